@@ -5,8 +5,8 @@
 One "step" = one `spartan.dot(A, B).force()` through the whole tile path (lazy DAG -> per-tile fp32 MFMA GEMM
 launches -> merge into the target), operands already resident in HBM:
 
-  --gpus 1 : BASELINE configs[1] -- dot 8192 x 8192 x 8192 fp32, one tile.  The same line carries the north-star
-             shape on one GPU (`northstar_32768`: dot 32768^3, timed with HIP events around whole `.force()` calls),
+  --gpus 1 : BASELINE configs[1] -- dot 8192 x 8192 x 8192 fp32, one tile.  With --full the same line carries the
+             north-star shape on one GPU (`northstar_32768`: dot 32768^3, timed with HIP events around whole `.force()` calls),
              the HBM-bound kernels, the k-means / lreg workloads of configs[3] / [4] on a per-GPU tile, and
              `ksplit_rank_emulation`: ONE rank's share of the p-GPU north-star step for p = 2, 4, 8, with every
              collective replaced by device copies of the same byte count on the communication stream (no multi-GPU
@@ -18,8 +18,13 @@ launches -> merge into the target), operands already resident in HBM:
              (spartan_amd/expr/dot.ksplit_pipeline).  `value` is whole-job TFLOP/s = 2 * 32768^3 * steps /
              max-over-ranks wall time; `dot_breakdown` gives kernel-only time and the bytes each GPU moved per step.
 
+A plain run (`--gpus N --steps K --warmup W`) measures the headline only: set-up, W warm-up steps, K timed steps,
+the line.  `--full` adds every other section (the extras named under --only, the CPU baseline and, at N > 1, the
+collectives' self-timing before the pipeline).  `--dump-outputs DIR` writes what the last timed step computed (a
+fixed, seeded sample of the result's rows and the float64 sum of every row; see dump_outputs) as DIR/<name>.npy.
+
 The line also carries the roofline of the dominant kernel (MFMA-bound GEMM; durations from HIP events on the launch
-stream) and the CPU baseline: the oracle's tile bodies on W = min(physical cores, 64) pinned one-thread worker
+stream) and, with --full, the CPU baseline: the oracle's tile bodies on W = min(physical cores, 64) pinned one-thread worker
 processes.  stdout gets the COMPACT line (tools/bench_line.py, < 10 KB: contract keys, compact roofline with every
 HBM section as [GB/s, fraction of measured copy], cpu_baseline, one summary per extra section); the detailed record
 -- raw sections, every emulation case, and `profile_table` (what every timed section launched: kernel, launches,
@@ -1083,16 +1088,43 @@ def _emit(record, rank):
   os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, (text + '\n').encode())
 
 
+DUMP_ROWS_BYTES = 32 << 20        # the row sample of --dump-outputs (C of the 8192^3 headline is 256 MiB)
+
+
+def dump_outputs(result, directory, rank):
+  """--dump-outputs: what the last timed step hands its caller, C = dot(A, B), as .npy files two builds can be
+  compared by: `dot_rows.npy`, the rows np.random.RandomState(SEED).choice picks (sorted; float32, 32 MiB at most),
+  and `dot_row_sums.npy`, the float64 sum of every row of C, so that every element counts.  The inputs come from
+  the seeded device generator, so the same arguments give the same A and B in every run.  glom() is collective:
+  every rank takes part, rank 0 writes."""
+  whole = np.asarray(result.glom())
+  if rank != 0:
+    return
+  rows, cols = whole.shape
+  pick = np.sort(np.random.RandomState(SEED).choice(rows, max(1, min(rows, DUMP_ROWS_BYTES // (4 * cols))), replace=False))
+  os.makedirs(directory, exist_ok=True)
+  np.save(os.path.join(directory, 'dot_rows.npy'), whole[pick].astype(np.float32))
+  np.save(os.path.join(directory, 'dot_row_sums.npy'), whole.sum(axis=1, dtype=np.float64))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=20)
   ap.add_argument('--warmup', type=int, default=3)
   ap.add_argument('--size', type=int, default=0, help='matrix order (default: 8192 on one GPU, 32768 on several)')
-  ap.add_argument('--no-extras', action='store_true', help='headline only: skip the HBM / workload / emulation / CPU sections')
-  ap.add_argument('--only', default='', help='comma-separated extras to run (northstar,hbm,dot_f64,gemm_shapes,host,lreg,kmeans,sparse,ksplit,tiles8,cpu; N > 1: hbm_dist,lreg_dist,kmeans_dist)')
+  ap.add_argument('--full', action='store_true',
+                  help='also run every other section: HBM / workload / emulation / CPU baseline (N > 1: collectives and the distributed sections)')
+  ap.add_argument('--no-extras', action='store_true', help='headline only, even with --full (a plain run is headline only)')
+  ap.add_argument('--only', default='', help='with --full: comma-separated extras to run (northstar,hbm,dot_f64,gemm_shapes,host,lreg,kmeans,sparse,ksplit,tiles8,cpu; N > 1: hbm_dist,lreg_dist,kmeans_dist)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                  help='write what the last timed step computed to DIR/<name>.npy (see dump_outputs)')
   ap.add_argument('--deadline', type=int, default=1500, help='seconds the self-launched ranks of --gpus N > 1 may take')
   args = ap.parse_args()
+  if args.only and not args.full:
+    ap.error('--only selects among the sections of --full: pass --full as well')
+  if args.steps < 1:
+    ap.error('--steps must be at least 1')
 
   if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
     sys.exit(self_launch(args.gpus, sys.argv[1:], args.deadline))      # plain `python3 bench.py --gpus N`
@@ -1126,7 +1158,8 @@ def main():
   A.force()
   B.force()
   collectives = None
-  if p > 1 and not args.no_extras:
+  extras = args.full and not args.no_extras
+  if p > 1 and extras:
     # every collective once, on its real message size, BEFORE the pipeline (a slow or hanging exchange shows here)
     collectives = guarded(lambda: collectives_section(ctx), 240, world.rank,
                           {'metric': 'spartan.dot TFLOP/s (+ map/reduce HBM GB/s)', 'value': None, 'unit': 'TFLOP/s',
@@ -1202,8 +1235,10 @@ def main():
         'note': 'bytes are what ONE GPU sends per step ((p-1)/p of its 4*M*N partial and of its A tile); the '
                 'reduce-scatters run on a communication stream behind the GEMM of the next chunk',
     }
+  if args.dump_outputs:
+    dump_outputs(keep[0], args.dump_outputs, world.rank)
   only = set(x for x in args.only.split(',') if x)
-  want = lambda name: not args.no_extras and (not only or name in only)   # noqa: E731
+  want = lambda name: extras and (not only or name in only)   # noqa: E731
   if world.rank == 0 and p == 1:
     del keep[:]
     D.trim_pool()

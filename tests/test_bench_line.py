@@ -115,3 +115,44 @@ def test_emit_writes_the_compact_line_and_the_detail_file(tmp_path, monkeypatch,
   bench._emit(full, 1)                           # other ranks print nothing
   out, err = capfd.readouterr()
   assert out == ''
+
+
+def test_dump_outputs_writes_a_bounded_seeded_sample(tmp_path):
+  """--dump-outputs on the 8192^3 headline's result: rows of C (float32) picked by a fixed seed and the float64 sum
+  of every row, 64 MB at most in all, written by rank 0 only, the same files for the same result."""
+  import numpy as np
+  import bench
+
+  class Result(object):
+    def __init__(self, a):
+      self.a = a
+
+    def glom(self):
+      return self.a
+
+  n = 8192
+  c = np.arange(n, dtype=np.float32)[:, None] + np.arange(n, dtype=np.float32)[None, :] * np.float32(0.5)   # row i starts with i
+  for d in ('a', 'b'):
+    bench.dump_outputs(Result(c), str(tmp_path / d), 0)
+  names = sorted(os.listdir(str(tmp_path / 'a')))
+  assert names == ['dot_row_sums.npy', 'dot_rows.npy']
+  rows, sums = np.load(str(tmp_path / 'a' / 'dot_rows.npy')), np.load(str(tmp_path / 'a' / 'dot_row_sums.npy'))
+  assert rows.dtype == np.float32 and sums.dtype == np.float64
+  assert rows.nbytes + sums.nbytes <= 64 << 20 and rows.shape[0] >= 256
+  picked = rows[:, 0].astype(np.int64)
+  assert (np.diff(picked) > 0).all()
+  np.testing.assert_array_equal(rows, c[picked])
+  np.testing.assert_array_equal(sums, c.sum(axis=1, dtype=np.float64))
+  for name in names:
+    np.testing.assert_array_equal(np.load(str(tmp_path / 'a' / name)), np.load(str(tmp_path / 'b' / name)))
+  bench.dump_outputs(Result(c), str(tmp_path / 'rank1'), 1)
+  assert not os.path.exists(str(tmp_path / 'rank1'))
+
+
+def test_only_names_sections_of_full():
+  """A plain run is the headline alone; --only picks among the sections of --full and is refused without it."""
+  import subprocess
+  import sys
+  p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--only', 'hbm'], capture_output=True, text=True,
+                     timeout=120, cwd=ROOT)
+  assert p.returncode == 2 and '--full' in p.stderr, p.stderr[-2000:]

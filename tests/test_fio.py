@@ -10,6 +10,14 @@ import pytest
 import spartan_amd as sp
 
 
+@pytest.fixture(autouse=True)
+def _checkpoints_in_tmp_path(tmp_path, monkeypatch):
+  """sp.checkpoint saves under CHECKPOINT_PATH, a fixed directory in the system temp directory that other users' and
+  earlier runs' files may hold: each test here checkpoints into its own temporary directory instead."""
+  import importlib
+  monkeypatch.setattr(importlib.import_module('spartan_amd.expr.checkpoint'), 'CHECKPOINT_PATH', str(tmp_path / 'checkpoint'))
+
+
 def _reference_style_tile_file(path, prefix, ul, lr, data):
   """fio.py:70-112 restated: magic, 2-byte LE dict length, str(dict) space-padded to 16 B, raw bytes."""
   tile_dict = {'dtype': str(data.dtype), 'shape': data.shape, 'type': "DENSITY", 'lr': lr, 'ul': ul}

@@ -100,7 +100,7 @@ def test_bench_eight_ranks_on_one_gpu_line():
   for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
     env.pop(k, None)
   p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--size', '4096', '--steps', '2',
-                      '--warmup', '1', '--deadline', '900'], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+                      '--warmup', '1', '--deadline', '900', '--full'], env=env, cwd=ROOT, stdout=subprocess.PIPE,
                      stderr=subprocess.PIPE, timeout=1000)
   out = p.stdout.decode('utf-8', 'replace').strip()
   assert p.returncode == 0, (out[-2000:], p.stderr.decode('utf-8', 'replace')[-4000:])

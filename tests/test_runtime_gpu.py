@@ -104,7 +104,7 @@ def test_bench_launches_its_own_ranks():
   env = dict(os.environ, SPARTAN_BENCH_DIST_ROWS='256', SPARTAN_BENCH_LREG_ROWS='4096', SPARTAN_BENCH_LREG_COLS='256',
              SPARTAN_BENCH_LREG_STEPS='3', SPARTAN_BENCH_KMEANS_POINTS='8192', SPARTAN_BENCH_KMEANS_K='64')
   out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--size', '2048', '--steps', '2',
-                        '--warmup', '1'], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        '--warmup', '1', '--full'], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
   text = out.stdout.decode('utf-8', 'replace').strip()
   assert out.returncode == 0, (text[-2000:], out.stderr.decode('utf-8', 'replace')[-3000:])
   lines = text.splitlines()

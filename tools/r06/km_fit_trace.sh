@@ -1,9 +1,10 @@
 #!/bin/bash
+ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/kmfit
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o km -- python $GRAFT_REPO_ROOT/bench.py --only kmeans --steps 2 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o km -- python $ROOT/bench.py --full --only kmeans --steps 2 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
 cd $GRAFT_REPO_ROOT
 f=$(ls $OUT/trace/*/*kernel_trace.csv $OUT/trace/*kernel_trace.csv 2>/dev/null | head -1)
 python tools/gaps.py $f 3 > $OUT/gaps.txt

@@ -1,6 +1,6 @@
-"""Roofline fractions recomputed from a rocprofv3 kernel trace of `python bench.py`.
+"""Roofline fractions recomputed from a rocprofv3 kernel trace of `python bench.py --full`.
 
-  rocprofv3 --kernel-trace --output-format csv -d DIR -o bench -- python bench.py > bench.json
+  rocprofv3 --kernel-trace --output-format csv -d DIR -o bench -- python bench.py --full > bench.json
   python tools/roofline.py --trace DIR/**/bench_kernel_trace.csv --bench bench.json \
          [--pmc PMC_DIR ...] --out-json profiles/rNN_roofline.json --out-csv profiles/rNN_bench_kernel_shapes.csv
 
