@@ -195,8 +195,7 @@ int sp_map_fused(const sp_program* prog, const void* const* d_inputs, void* d_ou
  * run on kernels specialised at build time on their instruction stream
  * (spartan_amd/csrc/sp_interp.hpp StaticProg); everything else runs on the
  * generic interpreter kernels.  Returns the library id the program would use,
- * or -1.  out_dtype < 0 = "any" (reductions).  SP_NO_STATIC=1 in the
- * environment disables the specialised kernels (A/B measurements). */
+ * or -1.  out_dtype < 0 = "any" (reductions). */
 int sp_program_static_id(const sp_program* prog, int32_t out_dtype);
 
 /* Run-time specialisation: a program OUTSIDE that library, applied to a large
@@ -342,8 +341,8 @@ int sp_rowdot_colsum_f32(const float* d_x, int64_t ldx, int64_t n, int64_t d, co
  *     contraction on the bf16 matrix pipe (three exact-product MFMAs per 16 features, fp32 accumulation,
  *     16 x the fp32 pipe's rate); its wider error window sends more points to the exact re-check: SAME labels
  *     (csrc/kmeans_split.hpp);
- *   SP_NEAREST_AUTO (0): split (>= 32 features, and >= 192 centers unless the points come prepared;
- *     SP_KM_SPLIT=0: fused) or fused for fp32 points when n*k*d >= 2^24, else exact.
+ *   SP_NEAREST_AUTO (0): split (>= 32 features, and >= 192 centers unless the points come prepared)
+ *     or fused for fp32 points when n*k*d >= 2^24, else exact.
  *   SP_NEAREST_FUSED_UNCHECKED (3) / SP_NEAREST_SPLIT_UNCHECKED (5): diagnostics only -- the filter alone; points it
  *     could not decide are left as -1 - (fp32 best) (used to report the re-check rate).
  * d_ws: sp_nearest_center_workspace_bytes(n, k, d) bytes of scratch.

@@ -24,26 +24,21 @@
 //   - B is kept [k][n]; fragments are 4 x ds_read_b32 (lanes along n);
 //   - XCD-aware block -> tile mapping: each XCD walks a contiguous range of the
 //     tile order, so the 64 workgroups resident on one XCD are neighbours and share
-//     their A panel in that XCD's private L2 (see SP_GEMM_GROUP_M).
+//     their A panel in that XCD's private L2 (see GROUP_M).
 #include "sp_common.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Tiles are walked m-fastest inside groups of SP_GEMM_GROUP_M tile rows.  Measured on 8192^3 (PMC, 2 x FETCH_SIZE,
-// the direct-to-LDS kernel of rounds 3+; round 6, tools/r06/gemm_group.sh): group 1 / 2 / 3 / 4 / 8 -> 9.19 / 6.76 /
+// Tiles are walked m-fastest inside groups of GROUP_M tile rows.  Measured on 8192^3 (PMC, 2 x FETCH_SIZE,
+// the direct-to-LDS kernel of rounds 3+; round 6): group 1 / 2 / 3 / 4 / 8 -> 9.19 / 6.76 /
 // 7.44 / 9.24 / 17.3 GB of L2 misses at the SAME speed (150.8 / 150.8 / 150.8 / 150.7 / 150.3 TFLOP/s; 32768^3,
 // 16384^3, 6144^3, 4096^3 and the pipeline's chunk shapes within 0.3 %): with two tile rows per group the 64
 // workgroups resident on an XCD are 2 A panels x 32 B panels instead of 1 x 64 -- half the B traffic for twice the
 // (small) A traffic; beyond 2 the workgroups of a group drift too far apart in k for the L2 to serve the shared
 // panels.  (Round 2, on the register-staged kernel, had measured 1 as the minimum: 10.1 GB against 10.6 for 2.)
 // 2 is the default since round 6: counter traffic at 8192^3 11.7 x -> 8.7 x the 12 n^2 floor.
-#ifndef SP_GEMM_ABLATE
-#define SP_GEMM_ABLATE 0      // build with -DSP_GEMM_ABLATE=1 for the timing-only variants (tools/gemm_variants.py)
-#endif
-#ifndef SP_GEMM_GROUP_M
-#define SP_GEMM_GROUP_M 2
-#endif
+constexpr int GROUP_M = 2;
 
 template <int BM, int BN, int BK, int WM, int WN>
 struct GemmCfg {
@@ -74,10 +69,10 @@ __device__ __forceinline__ void sp_gemm_tile_of_block(int bid, int nblk, int til
   const int xcd = bid & 7, local = bid >> 3;
   const int q = nblk >> 3, r = nblk & 7;
   const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-  const int per_group = SP_GEMM_GROUP_M * tiles_n;
+  const int per_group = GROUP_M * tiles_n;
   const int group = t / per_group;
-  const int first_m = group * SP_GEMM_GROUP_M;
-  const int gsize = (tiles_m - first_m) < SP_GEMM_GROUP_M ? (tiles_m - first_m) : SP_GEMM_GROUP_M;
+  const int first_m = group * GROUP_M;
+  const int gsize = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
   const int in_group = t - group * per_group;
   tm = first_m + (in_group % gsize);
   tn = in_group / gsize;
@@ -292,25 +287,26 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void sp_gemm_kernel(c
 // residue share their 16 banks, and the xor sends those four rows to four different chunks = four different bank
 // quads.  The B tile [16][BN] is read along n by ds_read_b32 exactly as before.
 // Preconditions (sp_gemm_f32 checks them, else the register-staged kernel runs): N % 4 == 0, lda % 4 == 0,
-// ldb % 4 == 0, 16-B aligned bases, K % 16 == 0.
+// ldb % 4 == 0, 16-B aligned bases, K >= 16 (a K % 16 tail goes through registers, see the kernel).
 template <int BM, int BN, int WM, int WN>
 struct GldsCfg {
   static constexpr int BK = 16;
   static constexpr int NW = WM * WN, THREADS = NW * 64;
   static constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 32, TN = WTN / 32;
   static constexpr int A_FLOATS = BM * BK, B_FLOATS = BK * BN, STAGE_FLOATS = A_FLOATS + B_FLOATS;
-  static constexpr int LDS_BYTES = 2 * STAGE_FLOATS * 4;    // (3 stages for the deep-prefetch variant)
+  static constexpr int LDS_BYTES = 2 * STAGE_FLOATS * 4;
   static constexpr int A_PIECES = (A_FLOATS / 256) / NW;   // 1 KiB wave-loads of A per wave and k-tile
   static constexpr int B_PIECES = (B_FLOATS / 256) / NW;
   static constexpr int MIN_WAVES = (NW == 4) ? 2 : 1;
   static_assert((A_FLOATS / 256) % NW == 0 && (B_FLOATS / 256) % NW == 0, "tile / waves mismatch");
 };
 
-// PIPE: the fragments of the two 8-deep halves of a k-tile live in two register sets; the half-tile that follows is
-// read from LDS while the current one is multiplied, and the workgroup barrier sits between the two halves (the
-// reads that must precede it were issued a half-tile of MFMAs earlier, the reads that follow it have one to land).
+// Measured and set aside (8192^3, profiles/r02_notes.md): three LDS stages with k-tiles requested two ahead, 149.1
+// against 150.2 TFLOP/s; the fragments of a k-tile's two 8-deep halves double-buffered in registers with the barrier
+// between the halves, 146.6.  k-tiles of 32 in the register-staged kernel (half the barriers per contraction) were
+// slower too (profiles/r01_notes.md).
 // WGS: workgroups per CU the register allocation aims for.
-template <typename Cfg, int BM, int BN, int WM, int WN, int PIPE, int WGS>
+template <typename Cfg, int BM, int BN, int WM, int WN, int WGS>
 __global__ __launch_bounds__(Cfg::THREADS, WGS) void sp_gemm_glds_kernel(
     const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, float* __restrict__ C,
     int64_t ldc, int M, int N, int K, int accumulate, int tiles_m, int tiles_n) {
@@ -391,135 +387,48 @@ __global__ __launch_bounds__(Cfg::THREADS, WGS) void sp_gemm_glds_kernel(
         _Pragma("unroll") for (int j = 0; j < TN; ++j)                                              \
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af_[i][s4], bf_[j][s4], acc[i][j], 0, 0, 0); \
   } while (0)
-  if constexpr (PIPE >= 16) {
-    SP_GLDS_TILE(0, 0);
-    SP_GLDS_LANDED();
-    __syncthreads();
-  } else if constexpr (PIPE == 3) {
-    // Three LDS stages, k-tiles requested TWO ahead: a tile has two k-tiles of MFMAs to land, so the tail of the
-    // load latency distribution (one slow 1 KiB piece of 24 holds the whole workgroup at its barrier) is covered.
-    // The wait is counted -- the AP + BP pieces of the newest tile stay in flight across the barrier -- which
-    // needs the raw barrier: __syncthreads() carries a fence that drains the LDS-DMA queue.
-    static_assert(AP + BP == 6 || AP + BP == 4, "vmcnt immediates below");
-#define SP_WAIT_BUT_NEWEST()                                                   \
-  do {                                                                         \
-    if constexpr (AP + BP == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); \
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                      \
-  } while (0)
-    auto body = [&](int t) {
+  SP_GLDS_TILE(0, 0);
+  SP_GLDS_LANDED();
+  __syncthreads();
+  for (int t = 0; t < nt; ++t) {
+    if (t + 1 < nt) SP_GLDS_TILE(t + 1, (t + 1) & 1);
 #pragma unroll
-      for (int c = 0; c < BK / 8; ++c) {
-        f32x4 af[TM];
-        float bf[TN][4];
-        SP_FRAGS(af, bf, t % 3, c);
-        SP_MFMAS(af, bf);
-      }
-    };
-    SP_GLDS_TILE(0, 0);
-    if (nt > 1) SP_GLDS_TILE(1, 1);
-    if (nt > 1) SP_WAIT_BUT_NEWEST();
-    else SP_GLDS_LANDED();
-    __builtin_amdgcn_s_barrier();
-    int t = 0;
-    for (; t + 2 < nt; ++t) {
-      SP_GLDS_TILE(t + 2, (t + 2) % 3);
-      body(t);
-      SP_WAIT_BUT_NEWEST();      // tile t+1 has landed; tile t+2 may still be on its way
-      __builtin_amdgcn_s_barrier();
+    for (int c = 0; c < BK / 8; ++c) {
+      f32x4 af[TM];
+      float bf[TN][4];
+      SP_FRAGS(af, bf, t & 1, c);
+      SP_MFMAS(af, bf);
     }
-    for (; t < nt; ++t) {
-      body(t);
-      SP_GLDS_LANDED();
-      __builtin_amdgcn_s_barrier();
-    }
-  } else if constexpr (PIPE) {
-    static_assert(BK == 16, "two fragment halves per k-tile");
-    f32x4 af0[TM], af1[TM];
-    float bf0[TN][4], bf1[TN][4];
-    SP_GLDS_TILE(0, 0);
-    if (nt > 1) SP_GLDS_TILE(1, 1);
     SP_GLDS_LANDED();
-    __syncthreads();
-    SP_FRAGS(af0, bf0, 0, 0);
-    for (int t = 0; t < nt; ++t) {
-      const int cur = t & 1;
-      SP_FRAGS(af1, bf1, cur, 1);
-      SP_MFMAS(af0, bf0);
-      // keep the first half's MFMAs AHEAD of the barrier (hipcc otherwise sinks them below it and the wave stalls
-      // on the LDS reads it has just issued): the barrier's lgkmcnt wait then finds them long finished
-      __builtin_amdgcn_sched_barrier(0);
-      SP_GLDS_LANDED();
-      __syncthreads();    // every wave has read all of stage `cur`; tile t+1 has landed in the other stage
-      if (t + 2 < nt) SP_GLDS_TILE(t + 2, cur);
-      if (t + 1 < nt) SP_FRAGS(af0, bf0, cur ^ 1, 0);
-      SP_MFMAS(af1, bf1);
+    __syncthreads();    // tile t+1 has landed and every wave is done reading stage t
+  }
+  // K tail (K % 16 != 0): the last, partial k-tile goes through registers into stage 0 in the same two images,
+  // zero beyond K in BOTH operands (so that whatever lies behind a row end never meets a product)
+  const int ktail = K - nt * BK;
+  if (ktail > 0) {
+    const int k0 = nt * BK;
+    for (int e = tid; e < BM * BK; e += Cfg::THREADS) {
+      const int r = e / BK, kk = e % BK;
+      int row = m0 + r;
+      if (row > M - 1) row = M - 1;
+      const float v = kk < ktail ? A[(int64_t)row * lda + k0 + kk] : 0.f;
+      smem[r * BK + (((kk >> 2) ^ ((r >> 2) & 3)) << 2) + (kk & 3)] = v;
     }
-  } else {
-    SP_GLDS_TILE(0, 0);
-    SP_GLDS_LANDED();
-    __syncthreads();
-    for (int t = 0; t < nt; ++t) {
-      if (t + 1 < nt) SP_GLDS_TILE(t + 1, (t + 1) & 1);
-#pragma unroll
-      for (int c = 0; c < BK / 8; ++c) {
-        f32x4 af[TM];
-        float bf[TN][4];
-        SP_FRAGS(af, bf, t & 1, c);
-        SP_MFMAS(af, bf);
-      }
-      SP_GLDS_LANDED();
-      __syncthreads();    // tile t+1 has landed and every wave is done reading stage t
+    for (int e = tid; e < BK * BN; e += Cfg::THREADS) {
+      const int kk = e / BN, c = e % BN;
+      int col = n0 + c;
+      if (col > N - 1) col = N - 1;
+      smem[Cfg::A_FLOATS + kk * BN + c] = kk < ktail ? B[(int64_t)(k0 + kk) * ldb + col] : 0.f;
     }
-    // K tail (K % 16 != 0): the last, partial k-tile goes through registers into stage 0 in the same two images,
-    // zero beyond K in BOTH operands (so that whatever lies behind a row end never meets a product)
-    const int ktail = K - nt * BK;
-    if (ktail > 0) {
-      const int k0 = nt * BK;
-      for (int e = tid; e < BM * BK; e += Cfg::THREADS) {
-        const int r = e / BK, kk = e % BK;
-        int row = m0 + r;
-        if (row > M - 1) row = M - 1;
-        const float v = kk < ktail ? A[(int64_t)row * lda + k0 + kk] : 0.f;
-        smem[r * BK + (((kk >> 2) ^ ((r >> 2) & 3)) << 2) + (kk & 3)] = v;
-      }
-      for (int e = tid; e < BK * BN; e += Cfg::THREADS) {
-        const int kk = e / BN, c = e % BN;
-        int col = n0 + c;
-        if (col > N - 1) col = N - 1;
-        smem[Cfg::A_FLOATS + kk * BN + c] = kk < ktail ? B[(int64_t)(k0 + kk) * ldb + col] : 0.f;
-      }
-      __syncthreads();
+    __syncthreads();
 #pragma unroll
-      for (int c = 0; c < BK / 8; ++c) {
-        f32x4 af[TM];
-        float bf[TN][4];
-        SP_FRAGS(af, bf, 0, c);
-        SP_MFMAS(af, bf);
-      }
+    for (int c = 0; c < BK / 8; ++c) {
+      f32x4 af[TM];
+      float bf[TN][4];
+      SP_FRAGS(af, bf, 0, c);
+      SP_MFMAS(af, bf);
     }
   }
-#if SP_GEMM_ABLATE
-  // Timing-only variants (SP_GEMM_VARIANT 16..23, results are WRONG by construction): which part of the k-loop the
-  // MFMA pipe waits for.  Bit 0: no k-tile loads after the first; bit 1: no barriers; bit 2: fragments read once;
-  // bit 3: loads issued but never waited for.
-  if constexpr (PIPE >= 16) {
-    constexpr int ABL = PIPE - 16;
-    f32x4 af[BK / 8][TM];
-    float bf[BK / 8][TN][4];
-    for (int t = 0; t < nt; ++t) {
-      if (!(ABL & 1) && t + 1 < nt) SP_GLDS_TILE(t + 1, (t + 1) & 1);
-#pragma unroll
-      for (int c = 0; c < BK / 8; ++c) {
-        if (!(ABL & 4) || t == 0) SP_FRAGS(af[c], bf[c], t & 1, c);
-        SP_MFMAS(af[c], bf[c]);
-      }
-      if (!(ABL & 2)) {
-        if (!(ABL & 8)) SP_GLDS_LANDED();
-        __syncthreads();
-      }
-    }
-  }
-#endif
 #undef SP_FRAGS
 #undef SP_MFMAS
 #undef SP_GLDS_TILE
@@ -543,21 +452,20 @@ __global__ __launch_bounds__(Cfg::THREADS, WGS) void sp_gemm_glds_kernel(
   }
 }
 
-template <int BM, int BN, int WM, int WN, int PIPE, int WGS>
+template <int BM, int BN, int WM, int WN, int WGS>
 static int sp_gemm_glds_launch(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
                                int64_t M, int64_t N, int64_t K, int acc, hipStream_t st) {
   using Cfg = GldsCfg<BM, BN, WM, WN>;
   const int64_t tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int64_t nblk = tiles_m * tiles_n;
   if (nblk > 2147483647LL) SP_FAIL("sp_gemm_f32: too many tiles");
-  auto k = sp_gemm_glds_kernel<Cfg, BM, BN, WM, WN, PIPE, WGS>;
-  constexpr int lds_bytes = (PIPE == 3 ? 3 : 2) * Cfg::STAGE_FLOATS * 4;
+  auto k = sp_gemm_glds_kernel<Cfg, BM, BN, WM, WN, WGS>;
   static bool attr_set = false;
   if (!attr_set) {
-    SP_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    SP_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES));
     attr_set = true;
   }
-  hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(Cfg::THREADS), lds_bytes, st, A, lda, B, ldb, C, ldc, (int)M,
+  hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(Cfg::THREADS), Cfg::LDS_BYTES, st, A, lda, B, ldb, C, ldc, (int)M,
                      (int)N, (int)K, acc, (int)tiles_m, (int)tiles_n);
   SP_CHECK_LAUNCH();
   return 0;
@@ -870,18 +778,6 @@ static int sp_gemm_launch(const float* A, int64_t lda, const float* B, int64_t l
 #undef SP_GEMM_ARGS
 }
 
-// Tuning knob (not part of the ABI contract): SP_GEMM_VARIANT=0..3 picks the
-// macro-tile; unset = the default chosen from rocprof measurements
-// (profiles/).
-static int sp_gemm_variant() {
-  static int v = -2;
-  if (v == -2) {
-    const char* e = getenv("SP_GEMM_VARIANT");
-    v = e ? atoi(e) : -1;
-  }
-  return v;
-}
-
 // The data-parallel macro-tile whose workgroups keep the CUs busy for the shorter time, and that time in units of one
 // 128 x 128 x K tile at the full CU rate.  A CU runs ceil(tiles / CUs) workgroups of its share; a 128 x 128
 // workgroup does half the work of a 256 x 128 one at ~0.93 of its rate (4 resident workgroups per CU instead of 2),
@@ -896,7 +792,7 @@ static int sp_gemm_dp_choice(int64_t M, int64_t N, double* cost) {
   const double cost_b = 2.0 * (double)cb * (cb == 1 ? 1.14 : 1.0);
   const double cost_s = (double)cs / 0.93 * (cs == 1 ? 1.08 : 1.0);
   const double cost_t = 0.5 * (double)ct / 0.90 * (ct == 1 ? 1.08 : 1.0);
-  int v = 6;
+  int v = 6;                // 6: 256 x 128, 7: 128 x 128, 8: 64 x 128
   *cost = cost_b;
   if (cost_s < *cost) v = 7, *cost = cost_s;
   if (cost_t < *cost) v = 8, *cost = cost_t;
@@ -920,44 +816,20 @@ extern "C" int sp_gemm_f32(const float* d_A, int64_t lda, const float* d_B, int6
   }
   const bool fast = (N % 4 == 0) && (N >= 4) && (lda % 4 == 0) && (ldb % 4 == 0) &&
                     ((((uintptr_t)d_A) | ((uintptr_t)d_B)) & 15) == 0;
-  int v = sp_gemm_variant();
-  if (v < 0) {
-    double cost;
-    v = sp_gemm_dp_choice(M, N, &cost);
-  }
-  switch (v) {
-    case 0: return sp_gemm_launch<256, 128, 16, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
-    case 1: return sp_gemm_launch<128, 128, 16, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
-    case 2: return sp_gemm_launch<256, 256, 16, 2, 4>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
-    case 3: return sp_gemm_launch<128, 256, 16, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
-    // (SP_GEMM_VARIANT only) k-tiles of 32 halve the barriers per contraction: slower, profiles/r01_notes.md
-    case 4: return sp_gemm_launch<128, 128, 32, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
-    case 5: return sp_gemm_launch<256, 128, 32, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
-    // direct-to-LDS k-tiles (preconditions checked here; otherwise the register-staged kernel of the same tile)
-    case 6: case 9: case 11:
-      if (fast && K >= 16 && (K % 16 == 0 || v == 6) && (int64_t)256 * lda < (1LL << 30) && (int64_t)16 * ldb < (1LL << 30)) {
-        if (v == 6) return sp_gemm_glds_launch<256, 128, 2, 2, 0, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, st);
-        if (v == 11) return sp_gemm_glds_launch<256, 128, 2, 2, 3, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, st);
-        // (SP_GEMM_VARIANT only) register double-buffered fragments, barrier between the k-tile's halves:
-        // 139.2 vs 141.5 TFLOP/s for case 6 -- profiles/r02_notes.md
-        return sp_gemm_glds_launch<256, 128, 2, 2, 1, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, st);
-      }
-      return sp_gemm_launch<256, 128, 16, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
-#if SP_GEMM_ABLATE
-#define SP_ABL_CASE(m) case 16 + m: return sp_gemm_glds_launch<256, 128, 2, 2, 16 + m, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, st);
-    SP_ABL_CASE(0) SP_ABL_CASE(1) SP_ABL_CASE(2) SP_ABL_CASE(3) SP_ABL_CASE(4) SP_ABL_CASE(5) SP_ABL_CASE(6) SP_ABL_CASE(7)
-    SP_ABL_CASE(8) SP_ABL_CASE(10)
-#undef SP_ABL_CASE
-#endif
+  double cost;
+  switch (sp_gemm_dp_choice(M, N, &cost)) {
     case 8:   // 64 x 128: twice the workgroups where 128 x 128 would leave one (or three) per CU
       if (fast && K >= 16 && (int64_t)128 * lda < (1LL << 30) && (int64_t)16 * ldb < (1LL << 30))
-        return sp_gemm_glds_launch<64, 128, 2, 2, 0, 4>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, st);
+        return sp_gemm_glds_launch<64, 128, 2, 2, 4>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, st);
       return sp_gemm_launch<128, 128, 16, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
     case 7:
       if (fast && K >= 16 && (int64_t)128 * lda < (1LL << 30) && (int64_t)16 * ldb < (1LL << 30))
-        return sp_gemm_glds_launch<128, 128, 2, 2, 0, 4>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, st);
+        return sp_gemm_glds_launch<128, 128, 2, 2, 4>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, st);
       return sp_gemm_launch<128, 128, 16, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
-    default: SP_FAIL("sp_gemm_f32: unknown SP_GEMM_VARIANT=%d", v);
+    default:  // 6: 256 x 128; direct-to-LDS k-tiles where the operands allow it, else the register-staged kernel
+      if (fast && K >= 16 && (int64_t)256 * lda < (1LL << 30) && (int64_t)16 * ldb < (1LL << 30))
+        return sp_gemm_glds_launch<256, 128, 2, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, st);
+      return sp_gemm_launch<256, 128, 16, 2, 2>(d_A, lda, d_B, ldb, d_C, ldc, M, N, K, accumulate, fast, st);
   }
 }
 
@@ -1020,7 +892,7 @@ static bool sp_sk_plan(int64_t M, int64_t N, int64_t K) {
     const char* e = getenv("SP_GEMM_SK");
     mode = e ? atoi(e) : -1;
   }
-  if (mode == 0 || sp_gemm_variant() >= 0) return false;
+  if (mode == 0) return false;
   if (K < 256 || N % 4 != 0 || N < 4) return false;
   const int64_t tb = ((M + 255) / 256) * ((N + 127) / 128);
   if (tb >= 2147483647LL) return false;

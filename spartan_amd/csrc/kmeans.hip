@@ -612,15 +612,14 @@ extern "C" size_t sp_nearest_center_workspace_bytes(int64_t n, int64_t k, int64_
 }
 
 // Which MFMA filter the AUTO / explicit tiers mean: the split tier wherever the fused one applies (fp32 points),
-// unless SP_KM_SPLIT=0 (A/B measurements) or the tier names the fp32 filter.
+// unless the tier names the fp32 filter.
 static bool km_use_split(int32_t tier, int64_t k, int64_t d, bool prepared) {
-  static const bool off = getenv("SP_KM_SPLIT") && atoi(getenv("SP_KM_SPLIT")) == 0;
   if (tier == SP_NEAREST_SPLIT || tier == SP_NEAREST_SPLIT_UNCHECKED) return true;
   if (tier == SP_NEAREST_FUSED || tier == SP_NEAREST_FUSED_UNCHECKED) return false;
   // few features: the terms the split leaves out outweigh the roundings it saves.  A stand-alone call also pays for
   // cutting the points, which few centers do not earn back (tools/km_tier_sweep.py: 1 250 000 x 64, k = 64: 0.42 ms
   // fp32 / 0.50 split / 0.21 with prepared points; from k = 256 on the split wins either way)
-  return !off && d >= 32 && (prepared || k >= 192);
+  return d >= 32 && (prepared || k >= 192);
 }
 
 extern "C" size_t sp_kmeans_points_prepared_bytes(int64_t n, int64_t d) { return 256 + km_points_split_bytes(n, d); }
@@ -710,28 +709,21 @@ static int km_nearest_center(const void* d_points, int32_t dtype, int64_t ldx, c
       if (sp_nearest_fused_launch((const float*)d_points, ldx, d_centers, cdtype, ldc, n, k, d, d_labels, w, st)) return 1;
     }
     if (tier == SP_NEAREST_FUSED_UNCHECKED || tier == SP_NEAREST_SPLIT_UNCHECKED) return 0;   // diagnostics: leave the marks (-1 - best) in place
-    // the points the fused kernel listed as undecided: fp32 window over all centers, exact fp64 distance
-    // for the few inside it (SP_KM_FULL_RECHECK=1: the full exact kernel instead, for A/B measurements)
-    static int recheck_mode = -1;   // 0: MFMA candidate masks (default); SP_KM_RECHECK=2: the exact kernel on the list
-    if (recheck_mode < 0) {
-      const char* e = getenv("SP_KM_RECHECK");
-      recheck_mode = e ? atoi(e) : 0;
-    }
+    // the points the fused kernel listed as undecided: the centers inside each one's window marked by the MFMA
+    // filter, exact fp64 distances to those
     rows = w.amb_rows;
     n_rows = w.amb_count;
-    if (recheck_mode == 0) {
-      if (split ? sp_nearest_split_mark_candidates(d, w, st) : sp_nearest_mark_candidates((const float*)d_points, ldx, d, w, st)) return 1;
-      if (cdtype == SP_F32)
-        hipLaunchKernelGGL((sp_nearest_candidates_kernel<float>), dim3(SP_CUS * 8), dim3(256), 0, st, (const float*)d_points,
-                           ldx, (const float*)d_centers, ldc, (int)w.kp, (int)k, (int)d, d_labels, rows, n_rows, w.cand_cap,
-                           w.cand_mask);
-      else
-        hipLaunchKernelGGL((sp_nearest_candidates_kernel<double>), dim3(SP_CUS * 8), dim3(256), 0, st, (const float*)d_points,
-                           ldx, (const double*)d_centers, ldc, (int)w.kp, (int)k, (int)d, d_labels, rows, n_rows, w.cand_cap,
-                           w.cand_mask);
-      SP_CHECK_LAUNCH();
-      handled = w.cand_cap;   // the exact kernel below only runs for a list the masks had no room for
-    }
+    if (split ? sp_nearest_split_mark_candidates(d, w, st) : sp_nearest_mark_candidates((const float*)d_points, ldx, d, w, st)) return 1;
+    if (cdtype == SP_F32)
+      hipLaunchKernelGGL((sp_nearest_candidates_kernel<float>), dim3(SP_CUS * 8), dim3(256), 0, st, (const float*)d_points,
+                         ldx, (const float*)d_centers, ldc, (int)w.kp, (int)k, (int)d, d_labels, rows, n_rows, w.cand_cap,
+                         w.cand_mask);
+    else
+      hipLaunchKernelGGL((sp_nearest_candidates_kernel<double>), dim3(SP_CUS * 8), dim3(256), 0, st, (const float*)d_points,
+                         ldx, (const double*)d_centers, ldc, (int)w.kp, (int)k, (int)d, d_labels, rows, n_rows, w.cand_cap,
+                         w.cand_mask);
+    SP_CHECK_LAUNCH();
+    handled = w.cand_cap;   // the exact kernel below only runs for a list the masks had no room for
   }
   const int64_t groups = (n + 7) / 8;   // 8 points per wave
   int64_t waves = rows ? (int64_t)SP_CUS * 16 : (groups < (int64_t)SP_CUS * 32 ? groups : (int64_t)SP_CUS * 32);

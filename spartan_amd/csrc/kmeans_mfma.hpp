@@ -619,8 +619,7 @@ static int sp_nearest_fused_launch(const float* X, int64_t ldx, const void* C, i
   // whole rounds walk all centers per workgroup; the workgroups of the partial last round are split over the centers
   // when that shortens it: `rem` workgroups of `tiles` blocks become rem * split of `per` blocks
   int64_t rem = blocks % KM_WG_SLOTS, split = 1, per = tiles;
-  static const bool tail_off = getenv("SP_KM_TAIL_SPLIT") && atoi(getenv("SP_KM_TAIL_SPLIT")) == 0;
-  if (rem > 0 && tiles > 1 && !tail_off) {
+  if (rem > 0 && tiles > 1) {
     split = tiles < KM_TAIL_SPLIT ? tiles : KM_TAIL_SPLIT;
     per = (tiles + split - 1) / split;
     split = (tiles + per - 1) / per;

@@ -44,15 +44,11 @@
 #pragma once
 
 typedef __bf16 km_bf16x8 __attribute__((ext_vector_type(8)));
-#ifndef KS_ABLATE
-#define KS_ABLATE 0     // timing-only builds (-DKS_ABLATE=n, tools/km_first.py): 1 no k-tile loads, 2 no fragment reads, 4 a
-                        // sixteenth of the epilogue (NB: the MFMAs whose results it no longer reads are dropped too), 8 no MFMAs, 16 point tiles from the L2
-#endif
 
 namespace {
 
 // Workgroup tile: 256 centers x (64 WN) points, 2 x WN waves of 128 centers x 64 points each, KS_BK features per
-// k-step.  Default: WN = 4 (512 lanes, ONE workgroup per CU, 130 KB of LDS) with 32 features per k-step -- 48 MFMAs per
+// k-step.  WN = 4 (512 lanes, ONE workgroup per CU, 130 KB of LDS) with 32 features per k-step -- 48 MFMAs per
 // wave and barrier; first pass at configs[3], one box: 1.74 ms against 1.82 for the fp32 kernel's geometry (WN = 2, 16
 // features, two workgroups per CU; 1.78 with a third LDS stage, k-tiles requested two k-steps ahead) and 1.86 for
 // WN = 4 with 16 features: what the wider tile loses to its 8-wave barrier the halved number of barriers more than
@@ -60,15 +56,12 @@ namespace {
 // parts removed 1.47 without the k-tile loads, 2.32 without the fragment reads, 2.00 without the MFMAs, 0.57 without all
 // of them; the k-tile-major layout of the images gave 20 % (the loads were waiting for lines the L2 had dropped, not
 // for bytes or issue slots).
-#ifndef KS_BK_FEATURES
-#define KS_BK_FEATURES 32     // (-DKS_BK_FEATURES=16: the round's first geometry, 256 x 128 tiles on two workgroups per CU)
-#endif
-constexpr int KS_BK = KS_BK_FEATURES;                          // features per k-step (and per slab of an image): 16 or 32
+constexpr int KS_WN = 4;                                       // WN of the workgroup tile
+constexpr int KS_BK = 32;                                      // features per k-step (and per slab of an image)
 constexpr int KS_RB = KS_BK * 2;                               // bytes of a row of a k-tile
 constexpr int KS_CH = KS_BK / 8;                               // its 16-byte chunks
 constexpr int KS_BM = KN_BM;
 constexpr int KS_A_BYTES = KS_BM * KS_RB;                      // one center image of a k-tile
-static_assert(KS_BK == 16 || KS_BK == 32, "k-tile");
 template <int WN>
 struct KsCfg {
   static constexpr int BN = 64 * WN, NW = 2 * WN, THREADS = 64 * NW;
@@ -78,10 +71,10 @@ struct KsCfg {
   static constexpr int SMEM_BYTES = STAGES * STAGE_BYTES + 2 * KS_BM * 4;   // + two |c|^2/2 slices
   static constexpr int APW = KS_A_BYTES / 1024 / NW;                    // 1-KiB pieces of a center image per wave
   static constexpr int BPW = B_BYTES / 1024 / NW;                       // ... of a point image
-  static constexpr int SLOTS = SP_CUS * (WN == 2 ? 2 : 1);             // resident workgroups
-  static_assert(SMEM_BYTES * (WN == 2 ? 2 : 1) <= 160 * 1024, "LDS budget of a CU");
+  static constexpr int SLOTS = SP_CUS;                                  // resident workgroups
+  static_assert(SMEM_BYTES <= 160 * 1024, "LDS budget of a CU");
   static_assert(APW >= 1 && BPW >= 1, "every wave brings pieces of both operands");
-  static_assert(SLOTS * BN == KM_TAIL_POINTS, "the tail buffer is sized for one round of either geometry");
+  static_assert(SLOTS * BN == KM_TAIL_POINTS, "the tail buffer is sized for one round");
 };
 
 __device__ __forceinline__ float km_split_factor(int d) { return 6.1f * (float)d + 1550.0f; }
@@ -281,14 +274,8 @@ __global__ __launch_bounds__(KsCfg<WN>::THREADS, 2) void sp_nearest_split_kernel
     }
   }
   // (PARTIAL launches pass the whole images and where their points start: first_point)
-  // (KS_ABLATE & 16: every workgroup reads the point tile of its XCD's first workgroup -- what the pass costs when the
-  // point images come from the L2)
-#ifndef KS_ABLATE_MOD
-#define KS_ABLATE_MOD 8
-#endif
-  const int m0_ld = (KS_ABLATE & 16) ? (int)(blockIdx.x % KS_ABLATE_MOD) * KS_BN : m0;
-  const char* __restrict__ Xh_blk = (const char*)(RECHECK ? Xh : Xh + (int64_t)(first_point + m0_ld) * KS_BK);
-  const char* __restrict__ Xm_blk = (const char*)(RECHECK ? Xm : Xm + (int64_t)(first_point + m0_ld) * KS_BK);
+  const char* __restrict__ Xh_blk = (const char*)(RECHECK ? Xh : Xh + (int64_t)(first_point + m0) * KS_BK);
+  const char* __restrict__ Xm_blk = (const char*)(RECHECK ? Xm : Xm + (int64_t)(first_point + m0) * KS_BK);
   const int64_t x_slab = (int64_t)n_total * KS_RB, c_slab = (int64_t)kp * KS_RB;   // bytes per k-tile of an image
   const unsigned s_base = SP_LDS_ADDR(smem);
   const unsigned chs_w = SP_LDS_ADDR(chs);
@@ -354,7 +341,7 @@ __global__ __launch_bounds__(KsCfg<WN>::THREADS, 2) void sp_nearest_split_kernel
   int t = 0;
   auto kstep = [&](auto first_of_block) {
     constexpr bool FIRST = decltype(first_of_block)::value;
-    const bool more = !(KS_ABLATE & 1) && t + 1 < steps;
+    const bool more = t + 1 < steps;
     KS_LOAD_BEGIN(nxt)
     const char* st = smem + cur * KS_STAGE_BYTES;
     // per 16 features of the k-tile: 24 MFMAs (mid x hi, hi x mid, hi x hi for the 4 x 2 tiles of the wave); a piece of
@@ -365,38 +352,24 @@ __global__ __launch_bounds__(KsCfg<WN>::THREADS, 2) void sp_nearest_split_kernel
       km_bf16x8 ah[4], am[4], bh[2], bm[2];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if (KS_ABLATE & 2) {
-          ah[i] = am[i] = *(const km_bf16x8*)(smem + a_frag[0]);
-          asm volatile("" : "+v"(ah[i]), "+v"(am[i]));
-          continue;
-        }
         ah[i] = *(const km_bf16x8*)(st + a_frag[kk] + i * 32 * KS_RB);
         am[i] = *(const km_bf16x8*)(st + KS_A_BYTES + a_frag[kk] + i * 32 * KS_RB);
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        if (KS_ABLATE & 2) {
-          bh[j] = bm[j] = *(const km_bf16x8*)(smem + b_frag[0]);
-          asm volatile("" : "+v"(bh[j]), "+v"(bm[j]));
-          continue;
-        }
         bh[j] = *(const km_bf16x8*)(st + b_frag[kk] + j * 32 * KS_RB);
         bm[j] = *(const km_bf16x8*)(st + KS_B_BYTES + b_frag[kk] + j * 32 * KS_RB);
       }
 #pragma unroll
       for (int idx = 0; idx < 24; ++idx) {
         const int term = idx >> 3, i = (idx & 7) >> 1, j = idx & 1;
-        if (!(KS_ABLATE & 8)) {
-          const km_bf16x8 a = term == 0 ? am[i] : ah[i];
-          const km_bf16x8 b = term == 1 ? bm[j] : bh[j];
-          if (FIRST && kk == 0 && term == 0) {
-            const km_f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, zero, 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[i][j], 0, 0, 0);
-          }
+        const km_bf16x8 a = term == 0 ? am[i] : ah[i];
+        const km_bf16x8 b = term == 1 ? bm[j] : bh[j];
+        if (FIRST && kk == 0 && term == 0) {
+          const km_f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, zero, 0, 0, 0);
         } else {
-          asm volatile("" : "+v"(acc[i][j]) : "v"(ah[i]), "v"(am[i]), "v"(bh[j]), "v"(bm[j]));
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[i][j], 0, 0, 0);
         }
         if (idx % 3 == 2 && piece < NPIECES) {
           __builtin_amdgcn_sched_barrier(0);
@@ -458,9 +431,9 @@ __global__ __launch_bounds__(KsCfg<WN>::THREADS, 2) void sp_nearest_split_kernel
     }
     const float before[2] = {best[0], best[1]};
 #pragma unroll
-    for (int i = 0; i < ((KS_ABLATE & 4) ? 1 : 4); ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int q = 0; q < ((KS_ABLATE & 4) ? 1 : 4); ++q) {
+      for (int q = 0; q < 4; ++q) {
         const km_f32x4 ch4 = *(const km_f32x4*)(chb + i * 32 + 8 * q);   // rows i*32 + 8q + 4lh + (0..3)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -580,19 +553,9 @@ static int km_split_go(dim3 grid, hipStream_t st, Args... args) {
   return 0;
 }
 
-static int km_split_wn() {
-  static int wn = -1;
-  if (wn < 0) {
-    const char* e = getenv("SP_KM_SPLIT_WN");
-    wn = e && atoi(e) == 2 ? 2 : 4;     // (2: only with -DKS_BK_FEATURES=16)
-  }
-  return wn;
-}
-
-template <int WN>
-static int sp_nearest_split_launch_wn(const void* C, int32_t cdtype, int64_t ldc, int64_t n, int64_t k, int64_t d,
-                                      int64_t* labels, const KmWorkspace& w, hipStream_t st) {
-  using K = KsCfg<WN>;
+static int sp_nearest_split_launch(const void* C, int32_t cdtype, int64_t ldc, int64_t n, int64_t k, int64_t d,
+                                   int64_t* labels, const KmWorkspace& w, hipStream_t st) {
+  using K = KsCfg<KS_WN>;
   const int64_t kp = w.kp, dp = w.dp;
   SP_HIP(hipMemsetAsync(w.cmax2, 0, 512, st));   // cmax2 and amb_count
   const unsigned pblocks = (unsigned)((kp + 3) / 4);   // one wavefront per center
@@ -605,8 +568,7 @@ static int sp_nearest_split_launch_wn(const void* C, int32_t cdtype, int64_t ldc
   SP_CHECK_LAUNCH();
   const int64_t blocks = (n + K::BN - 1) / K::BN, tiles = kp / KS_BM;
   int64_t rem = blocks % K::SLOTS, split = 1, per = tiles;
-  static const bool tail_off = getenv("SP_KM_TAIL_SPLIT") && atoi(getenv("SP_KM_TAIL_SPLIT")) == 0;
-  if (rem > 0 && tiles > 1 && !tail_off) {
+  if (rem > 0 && tiles > 1) {
     split = tiles < KM_TAIL_SPLIT ? tiles : KM_TAIL_SPLIT;
     per = (tiles + split - 1) / split;
     split = (tiles + per - 1) / per;
@@ -616,19 +578,19 @@ static int sp_nearest_split_launch_wn(const void* C, int32_t cdtype, int64_t ldc
   if (split == 1) rem = 0;
   const int64_t whole = blocks - rem, n_whole = whole * K::BN < n ? whole * K::BN : n;
   if (whole > 0 &&
-      km_split_go<false, false, WN>(dim3((unsigned)whole), st, (const __bf16*)w.Xh, (const __bf16*)w.Xm, (const float*)w.xn2,
-                                    (const __bf16*)w.Ch, (const __bf16*)w.Cm, (const float*)w.cn, (const unsigned*)w.cmax2,
-                                    (int)n_whole, (int)d, (int)dp, (int)kp, labels, w.amb_rows, w.amb_best, w.amb_count,
-                                    (unsigned*)nullptr, (float*)nullptr, 0, 0, 0, (int)n))
+      km_split_go<false, false, KS_WN>(dim3((unsigned)whole), st, (const __bf16*)w.Xh, (const __bf16*)w.Xm, (const float*)w.xn2,
+                                       (const __bf16*)w.Ch, (const __bf16*)w.Cm, (const float*)w.cn, (const unsigned*)w.cmax2,
+                                       (int)n_whole, (int)d, (int)dp, (int)kp, labels, w.amb_rows, w.amb_best, w.amb_count,
+                                       (unsigned*)nullptr, (float*)nullptr, 0, 0, 0, (int)n))
     return 1;
   if (rem > 0) {
     const int n_tail = (int)(n - n_whole);
-    if (km_split_go<false, true, WN>(dim3((unsigned)rem, (unsigned)split), st, (const __bf16*)w.Xh,
-                                     (const __bf16*)w.Xm, (const float*)w.xn2,
-                                     (const __bf16*)w.Ch, (const __bf16*)w.Cm, (const float*)w.cn,
-                                     (const unsigned*)w.cmax2, n_tail, (int)d, (int)dp, (int)kp, (int64_t*)nullptr,
-                                     (int*)nullptr, (float*)nullptr, (int*)nullptr, (unsigned*)nullptr, w.part,
-                                     KM_TAIL_POINTS, (int)per, (int)n_whole, (int)n))
+    if (km_split_go<false, true, KS_WN>(dim3((unsigned)rem, (unsigned)split), st, (const __bf16*)w.Xh,
+                                        (const __bf16*)w.Xm, (const float*)w.xn2,
+                                        (const __bf16*)w.Ch, (const __bf16*)w.Cm, (const float*)w.cn,
+                                        (const unsigned*)w.cmax2, n_tail, (int)d, (int)dp, (int)kp, (int64_t*)nullptr,
+                                        (int*)nullptr, (float*)nullptr, (int*)nullptr, (unsigned*)nullptr, w.part,
+                                        KM_TAIL_POINTS, (int)per, (int)n_whole, (int)n))
       return 1;
     hipLaunchKernelGGL(sp_nearest_merge_parts_kernel, dim3((unsigned)((n_tail + 255) / 256)), dim3(256), 0, st, w.part,
                        (int)split, KM_TAIL_POINTS, n_tail, (int)n_whole, 6.1f * (float)d + 1550.0f, w.cmax2, labels,
@@ -638,30 +600,15 @@ static int sp_nearest_split_launch_wn(const void* C, int32_t cdtype, int64_t ldc
   return 0;
 }
 
-static int sp_nearest_split_launch(const void* C, int32_t cdtype, int64_t ldc, int64_t n, int64_t k, int64_t d,
-                                   int64_t* labels, const KmWorkspace& w, hipStream_t st) {
-#if KS_BK_FEATURES == 16
-  if (km_split_wn() == 2) return sp_nearest_split_launch_wn<2>(C, cdtype, ldc, n, k, d, labels, w, st);
-#endif
-  return sp_nearest_split_launch_wn<4>(C, cdtype, ldc, n, k, d, labels, w, st);   // (32-feature k-tiles: this geometry only)
-}
-
 // Second pass over the listed points: marks the centers inside each point's error window.
-template <int WN>
-static int sp_nearest_split_mark_wn(int64_t d, const KmWorkspace& w, hipStream_t st) {
-  using K = KsCfg<WN>;
-  const dim3 grid((unsigned)((w.cand_cap + K::BN - 1) / K::BN), (unsigned)(w.kp / KS_BM));
-  return km_split_go<true, false, WN>(grid, st, (const __bf16*)w.Xh, (const __bf16*)w.Xm, (const float*)w.xn2,
-                                      (const __bf16*)w.Ch, (const __bf16*)w.Cm, (const float*)w.cn,
-                                      (const unsigned*)w.cmax2, (int)w.cand_cap, (int)d, (int)w.dp, (int)w.kp,
-                                      (int64_t*)nullptr, w.amb_rows, w.amb_best, w.amb_count, w.cand_mask, (float*)nullptr,
-                                      0, 0, 0, (int)w.n_points);
-}
 static int sp_nearest_split_mark_candidates(int64_t d, const KmWorkspace& w, hipStream_t st) {
-#if KS_BK_FEATURES == 16
-  if (km_split_wn() == 2) return sp_nearest_split_mark_wn<2>(d, w, st);
-#endif
-  return sp_nearest_split_mark_wn<4>(d, w, st);
+  using K = KsCfg<KS_WN>;
+  const dim3 grid((unsigned)((w.cand_cap + K::BN - 1) / K::BN), (unsigned)(w.kp / KS_BM));
+  return km_split_go<true, false, KS_WN>(grid, st, (const __bf16*)w.Xh, (const __bf16*)w.Xm, (const float*)w.xn2,
+                                         (const __bf16*)w.Ch, (const __bf16*)w.Cm, (const float*)w.cn,
+                                         (const unsigned*)w.cmax2, (int)w.cand_cap, (int)d, (int)w.dp, (int)w.kp,
+                                         (int64_t*)nullptr, w.amb_rows, w.amb_best, w.amb_count, w.cand_mask,
+                                         (float*)nullptr, 0, 0, 0, (int)w.n_points);
 }
 
 }  // namespace

@@ -71,40 +71,15 @@ static inline unsigned sp_grid_for(int64_t nvec, int U) {
   // (round 4, 2 GiB tile, 5-op chain: 8 / 16 / 32 workgroups per CU 1.23 / 1.18 / 1.16 ms, the whole tile 1.34;
   // round 5, after the trip lost its hoisted index conversions: 16 / 32 / 64 / 128 / 256 per CU and the whole tile
   // 1.00 / 0.97 / 0.93 / 0.98 / 1.01 / 1.20 ms, `x + 1` 0.85 / 0.84 / 0.77 / 0.77 / 0.74 / 0.90)
-  static int per_cu = -1;
-  if (per_cu < 0) {
-    const char* e = getenv("SP_INTERP_WG_PER_CU");
-    per_cu = e ? atoi(e) : 8 * SP_BLOCKS_PER_CU;
-  }
-  const int64_t cap = (int64_t)SP_CUS * per_cu;
-  if (per_cu > 0 && blocks > cap) blocks = cap;
+  constexpr int64_t cap = (int64_t)SP_CUS * 8 * SP_BLOCKS_PER_CU;
+  if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   return (unsigned)blocks;
-}
-
-// SP_NO_STATIC=1 forces the generic interpreter (A/B measurements, tests).
-int sp_static_enabled() {
-  static int v = -1;
-  if (v < 0) v = getenv("SP_NO_STATIC") ? 0 : 1;
-  return v;
 }
 
 // Reports which specialised kernel (if any) a program would run on; -1 = interpreter.
 extern "C" int sp_program_static_id(const sp_program* prog, int32_t out_dtype) {
   return prog ? sp_find_static(prog, out_dtype) : -1;
-}
-
-// Tuning knob: groups per lane for the vectorised fp32 paths (SP_MAP_UNROLL=1|2|4).
-static int sp_map_unroll() {
-  static int u = -1;
-  if (u < 0) {
-    const char* e = getenv("SP_MAP_UNROLL");
-    // two groups per lane: the dispatch (fetch, decode, branch) is shared by both; four need > 256 VGPRs
-    // (profiles/r04_notes.md: 5-op chain on the 2 GiB tile 1.21 / 1.11 / 2.2 ms at 1 / 2 / 4)
-    u = e ? atoi(e) : 2;
-    if (u != 1 && u != 2 && u != 4) u = 1;
-  }
-  return u;
 }
 
 template <typename T, int V, int U, bool LINEAR>
@@ -195,11 +170,10 @@ static int sp_map_go_jit(const sp_program* p, const sp_inputs& in, void* out, in
 template <typename T, int V, bool LINEAR>
 static int sp_map_go_u(const sp_program* p, const sp_inputs& in, void* out, int64_t start, int64_t nvec,
                        hipStream_t st) {
-  // multi-group variants are instantiated for the fp32 class only (the hot dtype)
+  // two groups per lane for the fp32 class (the hot dtype): the dispatch (fetch, decode, branch) is shared by both;
+  // four need > 256 VGPRs (profiles/r04_notes.md: 5-op chain on the 2 GiB tile 1.21 / 1.11 / 2.2 ms at 1 / 2 / 4)
   if constexpr (std::is_same<T, float>::value && V > 1) {
-    const int u = nvec >= 4 * SP_BLOCK * 64 ? sp_map_unroll() : 1;
-    if (u == 4) return sp_map_go<T, V, 4, LINEAR>(p, in, out, start, nvec, st);
-    if (u == 2) return sp_map_go<T, V, 2, LINEAR>(p, in, out, start, nvec, st);
+    if (nvec >= 4 * SP_BLOCK * 64) return sp_map_go<T, V, 2, LINEAR>(p, in, out, start, nvec, st);
   }
   return sp_map_go<T, V, 1, LINEAR>(p, in, out, start, nvec, st);
 }
@@ -217,7 +191,7 @@ static int sp_map_launch(const sp_program* p, const sp_inputs& in, const void* c
     (void)inp;
     int64_t nmain = (n / V) * V;
     if constexpr (std::is_same<T, float>::value) {
-      const int sid = sp_static_enabled() ? sp_find_static(p, p->out_dtype) : -1;
+      const int sid = sp_find_static(p, p->out_dtype);
       if (nmain && sid >= 0) {
         if (sp_map_go_static<true>(sid, p, in, out, nmain / V, st)) return 1;
         if (n - nmain && sp_map_go<T, 1, 1, true>(p, in, out, nmain, n - nmain, st)) return 1;
@@ -238,7 +212,7 @@ static int sp_map_launch(const sp_program* p, const sp_inputs& in, const void* c
   }
   if (sp_can_vectorize<V>(p, inp, out)) {
     if constexpr (std::is_same<T, float>::value) {
-      const int sid = sp_static_enabled() ? sp_find_static(p, p->out_dtype) : -1;
+      const int sid = sp_find_static(p, p->out_dtype);
       if (sid >= 0) {
         const int mask = sp_mask_2d(p, p->n_inputs);
         if (mask >= 0) {

@@ -28,22 +28,17 @@
 // kernels follow the program's flag at run time, the interpreter kernels (dispatch-bound) do without the hint.
 #define SP_RED_NTM(P) (P::kStatic ? 2 : 0)
 // the software-pipelined walk of the interpreted column kernel (sp_reduce_cols_kernel): groups of rows per dispatch
-// and operands held ahead (A/B builds: -DSP_RED_AHEAD_UP=.. -DSP_RED_AHEAD_N=..).  Measured on the 8192 x 65536 tile,
-// GB/s of sum((x - 0.5)^2, 0) / sum(x, 0) / max(2x + 1, 0) on the interpreter (tools/interp_reduce_time.py):
+// and operands held ahead.  Measured on the 8192 x 65536 tile, GB/s of sum((x - 0.5)^2, 0) / sum(x, 0) /
+// max(2x + 1, 0) on the interpreter:
 //   no pipeline (round 4)  2196 / 3856 / 1709       UP 2, N 2 (174 VGPRs: 2 waves per SIMD)  1744 / 3856 / 1709
 //   UP 2, N 1 (167: 3)     2229 / 5181 / 2261       UP 1, N 1   1810 / 4350 / 1879           UP 4, N 1 (256: 1)  1283 / 2515 / 1170
 // -- one operand ahead at three waves per SIMD; programs of two operands take the plain walk.  What is left is the
 // dispatch itself (the interpreted instructions of one trip cost more than its 16 bytes per lane take to arrive).
-#ifndef SP_RED_AHEAD_UP
-#define SP_RED_AHEAD_UP 2
-#endif
-#ifndef SP_RED_AHEAD_N
-#define SP_RED_AHEAD_N 1
-#endif
+constexpr int kRedAheadUp = 2;
+constexpr int kRedAheadN = 1;
 
 #ifndef __HIPCC_RTC__
 int sp_validate_program(const sp_program* p);
-int sp_static_enabled();
 #include "sp_jit.hpp"
 #endif
 
@@ -260,13 +255,13 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_reduce_rows_kernel(const sp_progr
       // trip t + 1 requested before trip t's program is dispatched; UP groups share a dispatch).  The plain loop below
       // issued 0.8 scalar instructions per ELEMENT (addressing and operand-type decisions of every trip) and was bound
       // by scalar issue, not by HBM or the vector ALU (profiles/r05_notes.md section 10).
-      if (sp_ahead_applies<T, SP_RED_AHEAD_N>(p)) {
+      if (sp_ahead_applies<T, kRedAheadN>(p)) {
         walked = true;
-        constexpr int UP = SP_RED_AHEAD_UP;
+        constexpr int UP = kRedAheadUp;
         constexpr int64_t step = (int64_t)SP_BLOCK * V;
         int64_t a = a0 + (int64_t)threadIdx.x * V;
         if (a + V <= a1) {
-          sp_ahead<T, V, UP, SP_RED_AHEAD_N> ah;
+          sp_ahead<T, V, UP, kRedAheadN> ah;
           auto place = [&](int64_t at, int64_t (&Lo)[UP]) {
 #pragma unroll
             for (int u = 0; u < UP; ++u) {
@@ -461,11 +456,11 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_reduce_cols_kernel(const sp_progr
       // the interpreted map (sp_ahead, map_kernel.hpp) -- the operands of trip t + 1 are requested once trip t's sit
       // in the register file and before its program is dispatched, so HBM works while the wave interprets.  UP groups
       // of rows share a dispatch.
-      if (sp_ahead_applies<T, SP_RED_AHEAD_N>(p)) {
+      if (sp_ahead_applies<T, kRedAheadN>(p)) {
         walked = true;
-        constexpr int UP = SP_RED_AHEAD_UP;
+        constexpr int UP = kRedAheadUp;
         if (active && a0 + w < a1) {
-          sp_ahead<T, V, UP, SP_RED_AHEAD_N> ah;
+          sp_ahead<T, V, UP, kRedAheadN> ah;
           auto place = [&](int64_t at, int64_t (&Lo)[UP]) {
 #pragma unroll
             for (int u = 0; u < UP; ++u) {
@@ -631,17 +626,8 @@ struct RedPlan {
   int64_t partial_slots;  // number of (val[,idx]) partial slots needed
 };
 
+// workgroups the planner aims for when it splits the reduced axis
 static const int64_t kTargetBlocks = (int64_t)SP_CUS * SP_BLOCKS_PER_CU;
-
-// workgroups the planner aims for when it splits the reduced axis (SP_RED_TARGET: tuning knob)
-static int64_t sp_plan_target() {
-  static int64_t v = -1;
-  if (v < 0) {
-    const char* e = getenv("SP_RED_TARGET");
-    v = e ? atoll(e) : kTargetBlocks;
-  }
-  return v;
-}
 
 static RedPlan sp_plan(int V, int64_t O, int64_t A, int64_t I) {
   RedPlan pl;
@@ -656,7 +642,7 @@ static RedPlan sp_plan(int V, int64_t O, int64_t A, int64_t I) {
     pl.kind = 0;
     const int64_t unit = (int64_t)SP_BLOCK * V;  // one pass of the workgroup
     const int64_t min_chunk = unit * 8;
-    int64_t want = (sp_plan_target() + O - 1) / O;       // splits needed to fill the chip
+    int64_t want = (kTargetBlocks + O - 1) / O;       // splits needed to fill the chip
     int64_t maxs = (A + min_chunk - 1) / min_chunk;   // splits the row can afford
     int64_t ns = want < maxs ? want : maxs;
     if (ns < 1) ns = 1;
@@ -673,7 +659,7 @@ static RedPlan sp_plan(int V, int64_t O, int64_t A, int64_t I) {
   pl.kind = 2;
   const int64_t bx = (I + 64 * V - 1) / (64 * V);
   const int64_t min_chunk = (SP_BLOCK / 64) * 16;
-  int64_t want = (sp_plan_target() + bx * O - 1) / (bx * O);
+  int64_t want = (kTargetBlocks + bx * O - 1) / (bx * O);
   int64_t maxs = (A + min_chunk - 1) / min_chunk;
   int64_t ns = want < maxs ? want : maxs;
   if (ns < 1) ns = 1;
@@ -731,7 +717,7 @@ static int sp_reduce_launch(const sp_program* p, const sp_inputs& in, const void
   // x*x, x*x+x, x*(yp-y); arg-reductions of x.
   int sid = -1;
   if constexpr (sp_is_same<T, float>::value) {
-    if (vec && sp_static_enabled()) {
+    if (vec) {
       sid = sp_find_static(p, -1);
       if (kArg ? (sid != 0) : !(sid == 0 || sid == 7 || sid == 9 || sid == 10 || sid == 11)) sid = -1;
     }

@@ -380,8 +380,6 @@ int sort_lds64(const T* in, int64_t rows, int64_t cols, T* out_vals, int64_t* ou
 
 // segmented passes keep one histogram per (line, digit, key block of the line)
 inline bool seg_ok(int64_t rows, int64_t cols) {
-  const char* e = getenv("SP_SORT_SEGMENTED");     // "0": force the row passes (test knob)
-  if (e && e[0] == '0') return false;
   // a segment occupies whole key blocks of 4096: lines below 2048 would leave most of every block empty (256-wide
   // fp64 lines: 120 ms segmented against ~36 ms with the row passes)
   return cols >= 2048 && sp_sort_blocks(rows * cols, cols) * RDX <= rows * cols;

@@ -60,8 +60,8 @@ static inline size_t sp_dtype_size(int32_t dt) {
 // and the wave's 1 KiB lands at a wave-uniform LDS base + 16 * lane.
 #ifndef __HIPCC_RTC__
 // An LDS-DMA is complete for OTHER waves only after the issuing wave has waited for it (vmcnt) and a barrier: hipcc
-// does not reliably put that wait in front of a barrier inside a loop (seen missing in the PIPE loop's .s), so
-// it is stated here.
+// does not reliably put that wait in front of a barrier inside a loop (seen missing in the .s of a software-pipelined
+// k-loop), so it is stated here.
 #define SP_GLDS_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 // `global_load_lds_dwordx4 v_off, s[base:base+1]`: a wave-uniform 64-bit base in SGPRs plus an unsigned 32-bit
 // per-lane byte offset, LDS target (a wave-uniform byte address) through M0.  Written in asm because hipcc selects

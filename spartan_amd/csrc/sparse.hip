@@ -271,10 +271,10 @@ __global__ __launch_bounds__(256) void sp_csr_spmv_plan_kernel(const int64_t* __
 // SPMV_SPILL entries after the chunk, the plan's row range and, right behind it, the row pointers of the thread's
 // own row -- then the gathers of x, one barrier, and the row sums from LDS.
 // What bounds it (900 000 pages x 10 links, MI355X): 51.6 us, of which the random gather of x is 29 -- with x read
-// at the entry's own position instead (SP_SPMV_ABLATE=1, timing only) the same launch takes 22.5 us = 3.85 TB/s of
-// the algorithmic bytes.  Every gathered 4-byte value moves a whole cache line from the L2 to the CU (9 M lines
-// per launch); the entry stream itself is not the limit, and non-temporal entry loads (SP_SPMV_NT=1) cut the
-// counter traffic from 1.65 x to 1.33 x algorithmic but run slower (62 us).
+// at the entry's own position instead (a timing-only build) the same launch takes 22.5 us = 3.85 TB/s of the
+// algorithmic bytes.  Every gathered 4-byte value moves a whole cache line from the L2 to the CU (9 M lines per
+// launch); the entry stream itself is not the limit, and non-temporal entry loads cut the counter traffic from 1.65 x
+// to 1.33 x algorithmic but run slower (62 us against 52).
 //   * longest row <= SPMV_SPILL + 1 (the plan knows): a row belongs to the chunk it STARTS in and is summed whole
 //     there, in storage order; what spills over the chunk's end is in the extra entries every workgroup loaded.
 //     No carries, no second pass.
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void sp_csr_spmv_plan_kernel(const int64_t* __
 //     floating-point atomics, and still one launch.
 constexpr int SPMV_SPILL = 64;
 
-template <typename T, bool NT, bool ABLATE_GATHER = false>
+template <typename T>
 __global__ __launch_bounds__(256) void sp_csr_spmv_planned_kernel(const int64_t* __restrict__ indptr,
                                                                   const int32_t* __restrict__ indices,
                                                                   const T* __restrict__ vals,
@@ -309,8 +309,8 @@ __global__ __launch_bounds__(256) void sp_csr_spmv_planned_kernel(const int64_t*
     v[u] = 0;
     col[u] = 0;
     if (e < e1) {
-      v[u] = NT ? __builtin_nontemporal_load(vals + e) : vals[e];
-      col[u] = NT ? __builtin_nontemporal_load(indices + e) : indices[e];
+      v[u] = vals[e];
+      col[u] = indices[e];
     }
   }
   T vs = 0;
@@ -327,11 +327,8 @@ __global__ __launch_bounds__(256) void sp_csr_spmv_planned_kernel(const int64_t*
     rb = indptr[r + 1];
   }
 #pragma unroll
-  for (int u = 0; u < SPMV_CH / 256; ++u) {
-    // (timing ablation only: x read at the entry's own position instead of its column -- a coalesced stream)
-    const int64_t xi = ABLATE_GATHER ? (e0 + u * 256 + tid) % m : (int64_t)col[u];
-    prod[u * 256 + tid] = x ? v[u] * x[xi * ldx] : v[u];     // (a non-temporal gather of x: 80 us instead of 52)
-  }
+  for (int u = 0; u < SPMV_CH / 256; ++u)
+    prod[u * 256 + tid] = x ? v[u] * x[(int64_t)col[u] * ldx] : v[u];     // (a non-temporal gather of x: 80 us instead of 52)
   if (tid < SPMV_SPILL) prod[SPMV_CH + tid] = spill ? (x ? vs * x[(int64_t)cs * ldx] : vs) : (T)0;
   __syncthreads();
   if (whole_rows) {
@@ -674,19 +671,9 @@ int spmm_go(int64_t m, int64_t n, int64_t nnz, const int64_t* indptr, const int3
       T* carry = (T*)ws;
       int64_t* carry_row = (int64_t*)((char*)ws + sp_al256((size_t)nchunk * sizeof(T)));
       const int per = (nchunk + 7) / 8;
-      const char* ep = getenv("SP_SPMV_PLANNED");      // "0": the two-launch form even with a plan (A/B knob)
-      if (plan && !(ep && ep[0] == '0')) {
-        const char* en = getenv("SP_SPMV_NT");
-        const char* ab = getenv("SP_SPMV_ABLATE");        // timing-only: wrong results
-        if (ab && ab[0] == '1')
-          hipLaunchKernelGGL((sp_csr_spmv_planned_kernel<T, false, true>), dim3(per * 8), dim3(256), 0, st, indptr, indices, vals, B, ldb,
-                             C, ldc, m, nnz, nchunk, accumulate, carry, carry_row, const_cast<int64_t*>(plan));
-        else if (!(en && en[0] == '1'))      // default: plain loads (non-temporal entry loads measured slower here: 62 vs 52 us)
-          hipLaunchKernelGGL((sp_csr_spmv_planned_kernel<T, false>), dim3(per * 8), dim3(256), 0, st, indptr, indices, vals, B, ldb,
-                             C, ldc, m, nnz, nchunk, accumulate, carry, carry_row, const_cast<int64_t*>(plan));
-        else
-          hipLaunchKernelGGL((sp_csr_spmv_planned_kernel<T, true>), dim3(per * 8), dim3(256), 0, st, indptr, indices, vals, B, ldb,
-                             C, ldc, m, nnz, nchunk, accumulate, carry, carry_row, const_cast<int64_t*>(plan));
+      if (plan) {
+        hipLaunchKernelGGL((sp_csr_spmv_planned_kernel<T>), dim3(per * 8), dim3(256), 0, st, indptr, indices, vals, B, ldb,
+                           C, ldc, m, nnz, nchunk, accumulate, carry, carry_row, const_cast<int64_t*>(plan));
         SP_CHECK_LAUNCH();
         return 0;
       }

@@ -30,7 +30,7 @@ namespace {
 // 37.4 us on the 900 000-page tile; the row of a direct entry packed into its key: 35.8 us.
 // Round 6: the loop's loads really run ahead now (see the kernel: three entry sets, two gather sets and two slice sets
 // taking turns, nothing moved between them; two LDS slice buffers, so that a segment's slice is stored while the chunk
-// before is multiplied and needs no barrier of its own).  Timed with parts removed (-DBSP_ABLATE, one box, us):
+// before is multiplied and needs no barrier of its own).  Timed with parts removed (timing-only builds, one box, us):
 //   whole kernel 33.4 | no chunk loop at all 7.7 | loop without products and run sums 23.7 (27.1 before this round's
 //   pipeline) | ... and without its barriers 22.3 | loop without barriers only 28.9
 // i.e. 7.7 fixed + 16 for the loop's loads (72 MB of entries, 113 MB of slices through the L2, the direct gathers:
@@ -223,10 +223,6 @@ __global__ __launch_bounds__(BSP_THREADS) void sp_bsp_build_kernel(const int64_t
 }
 
 typedef float bsp_f4 __attribute__((ext_vector_type(4)));
-#ifndef BSP_ABLATE
-#define BSP_ABLATE 0    // timing-only builds (wrong results): 1 no chunk loop, 2 no run sums, 4 no products, 8 no barriers in the loop
-#endif
-
 // (second launch bound: waves per SIMD -- two workgroups of 8 waves per CU)
 template <bool PACKED>
 __global__ __launch_bounds__(BSP_THREADS, 4 / BSP_WGS_PER_CU * BSP_WGS_PER_CU) void sp_bsp_spmv_kernel(const int64_t* __restrict__ indptr, int64_t m, int rb,
@@ -392,9 +388,7 @@ __global__ __launch_bounds__(BSP_THREADS, 4 / BSP_WGS_PER_CU * BSP_WGS_PER_CU) v
     uint16_t* rbuf = rid + buf * BSP_CAP;
     bsp_f4 p = {0.f, 0.f, 0.f, 0.f};
     u16x4 r = {0, 0, 0, 0};
-    if (BSP_ABLATE & 4) {
-      asm volatile("" ::"v"(A.k), "v"(A.v), "v"(X), "v"(A.r));
-    } else if (i0 < cur.cnt) {
+    if (i0 < cur.cnt) {
 #pragma unroll
       for (int u = 0; u < BSP_PER; ++u) {
         const float xv = cur.staged ? xc[A.k[u] & 0xffffu] : X[u];
@@ -419,14 +413,14 @@ __global__ __launch_bounds__(BSP_THREADS, 4 / BSP_WGS_PER_CU * BSP_WGS_PER_CU) v
     c1 = c2;
     c2 = c3;
     c3 = next_chunk(c3);
-    if (!(BSP_ABLATE & 8)) __syncthreads();
+    __syncthreads();
     // the iteration's requests, around the run sums rather than in one burst ahead of the barrier (33.0 -> 32.2 us:
     // the vector-memory path works on the slice while the waves are busy in LDS)
     prefetch_slice(c2.seg, c2.fresh, XR);
     __builtin_amdgcn_sched_barrier(0);                   // products of `done` (and the next slice) are in LDS; everybody is past the runs before
     // Runs of equal rows: the lane holding a run's first entry adds the run, in order, to the row's accumulator --
     // its own entries from registers, what continues in later lanes' entries from LDS.
-    if (!(BSP_ABLATE & 2) && i0 < done.cnt) {
+    if (i0 < done.cnt) {
       // (the lane's own products and rows are still in its registers; LDS holds them for the other lanes)
       const int nvalid = done.cnt - i0;                       // >= 1; entries u >= nvalid are not this chunk's
       const unsigned prev = i0 == 0 ? 0xffffffffu : (unsigned)rbuf[i0 - 1];
@@ -465,7 +459,6 @@ __global__ __launch_bounds__(BSP_THREADS, 4 / BSP_WGS_PER_CU * BSP_WGS_PER_CU) v
   };
   // chunk j: entries in set j % 3, gathers in set j % 2; the six combinations in turn, no register ever moves
   for (;;) {
-    if (BSP_ABLATE & 1) break;
     if (!(cur.seg < n)) break;
     step(E0, E2, X0, xr1);
     if (!(cur.seg < n)) break;

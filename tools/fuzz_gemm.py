@@ -1,5 +1,5 @@
-"""Random shapes / paddings / accumulate flags of sp_gemm_f32 with small-integer operands: every product must be exact
-(SP_GEMM_VARIANT pins a kernel).  Usage: python tools/fuzz_gemm.py [seed]"""
+"""Random shapes / paddings / accumulate flags of sp_gemm_f32 with small-integer operands: every product must be exact.
+Usage: python tools/fuzz_gemm.py [seed]"""
 import sys
 import time
 

@@ -1,5 +1,5 @@
 """Times sp_nearest_center on BASELINE configs[3]'s tile (1.25 M x 256 points, 1024 centres) -- the number DESIGN.md
-quotes for the assign step.  SP_KM_TAIL_SPLIT=0 turns the split of the last workgroup round off."""
+quotes for the assign step."""
 import numpy as np
 
 from _dev import D, kernels, rand, timeit
