@@ -68,6 +68,36 @@ constexpr int32_t SP_PAD_IDX32 = 1, SP_PAD_STREAM = 2;
 #define SP_STREAMS(NTM, p) ((NTM) == 1 || ((NTM) == 2 && ((p).pad & SP_PAD_STREAM) != 0))
 constexpr int64_t SP_STREAM_ELEMS = 8LL << 20;   // 32 MiB of fp32 = the aggregate L2
 
+// ---- float -> integer conversions as x86 NumPy performs them (ndarray.astype: cvttss2si / cvttsd2si) ----
+// Truncation toward zero; NaN, +-inf and values outside the target range give INT_MIN of the target width (C leaves
+// them undefined, and v_cvt_i32_f32 would saturate them and map NaN to 0).  uint8 goes through int32 as x86 does:
+// 300.0 -> 44, -1.0 -> 255, NaN -> 0.
+template <typename F>
+__device__ __forceinline__ int32_t sp_f2i32(F x) {
+  return (x > (F)-2147483649.0 && x < (F)2147483648.0) ? (int32_t)x : (int32_t)INT32_MIN;
+}
+template <typename F>
+__device__ __forceinline__ int64_t sp_f2i64(F x) {
+  return (x >= (F)-9223372036854775808.0 && x < (F)9223372036854775808.0) ? (int64_t)x : (int64_t)INT64_MIN;
+}
+// a value of the arithmetic type T converted to the storage type I (int32_t / int64_t / uint8_t): integers wrap
+template <typename I, typename T>
+__device__ __forceinline__ I sp_to_int(T x) {
+  if constexpr (sp_is_integral<T>::value) {
+    return (I)x;
+  } else if constexpr (sizeof(I) == 8) {
+    return (I)sp_f2i64(x);
+  } else {
+    return (I)sp_f2i32(x);
+  }
+}
+// an operand element of type S converted to the arithmetic type T (a float operand of an integer class: astype)
+template <typename T, typename S>
+__device__ __forceinline__ T sp_cvt(S x) {
+  if constexpr (sp_is_integral<T>::value && !sp_is_integral<S>::value) return (T)sp_f2i64(x);
+  else return (T)x;
+}
+
 // ---- typed loads: `n` consecutive elements (n == V, or 1) converted to T ----
 // NT: the operand is read exactly once by the whole launch (no broadcast dimension), so its lines need not stay in
 // L2: non-temporal vector loads (`global_load_dwordx4 ... nt`).  On the 2 GiB tile this is worth 6.0 -> 6.6-6.8 TB/s
@@ -94,24 +124,24 @@ __device__ __forceinline__ void sp_load_vec(const void* base, int32_t dt, int64_
       const float* p = (const float*)base + off;
       if constexpr (N == 4) {
         sp_f32x4u v = SP_VLD(sp_f32x4u, p);
-        dst[0] = (T)v.x; dst[1] = (T)v.y; dst[2] = (T)v.z; dst[3] = (T)v.w;
+        dst[0] = sp_cvt<T>(v.x); dst[1] = sp_cvt<T>(v.y); dst[2] = sp_cvt<T>(v.z); dst[3] = sp_cvt<T>(v.w);
       } else if constexpr (N == 2) {
         sp_f32x2u v = SP_VLD(sp_f32x2u, p);
-        dst[0] = (T)v.x; dst[1] = (T)v.y;
+        dst[0] = sp_cvt<T>(v.x); dst[1] = sp_cvt<T>(v.y);
       } else {
-        dst[0] = (T)p[0];
+        dst[0] = sp_cvt<T>(p[0]);
       }
     } break;
     case SP_F64: {
       const double* p = (const double*)base + off;
       if constexpr (N == 4) {
         sp_f64x2u v0 = SP_VLD(sp_f64x2u, p), v1 = SP_VLD(sp_f64x2u, (p + 2));
-        dst[0] = (T)v0.x; dst[1] = (T)v0.y; dst[2] = (T)v1.x; dst[3] = (T)v1.y;
+        dst[0] = sp_cvt<T>(v0.x); dst[1] = sp_cvt<T>(v0.y); dst[2] = sp_cvt<T>(v1.x); dst[3] = sp_cvt<T>(v1.y);
       } else if constexpr (N == 2) {
         sp_f64x2u v = SP_VLD(sp_f64x2u, p);
-        dst[0] = (T)v.x; dst[1] = (T)v.y;
+        dst[0] = sp_cvt<T>(v.x); dst[1] = sp_cvt<T>(v.y);
       } else {
-        dst[0] = (T)p[0];
+        dst[0] = sp_cvt<T>(p[0]);
       }
     } break;
     case SP_I32: {
@@ -153,11 +183,6 @@ __device__ __forceinline__ void sp_load_vec(const void* base, int32_t dt, int64_
   }
 }
 
-template <typename T>
-__device__ __forceinline__ int64_t sp_to_i64(T x) {
-  return (int64_t)x;
-}
-
 // ---- typed stores with the NumPy cast semantics of ndarray.astype ----
 // NT: the output of a launch bigger than the L2 (non-temporal 16-B stores: 6.42 -> 6.51 TB/s on the 2 GiB map)
 #define SP_VST(TYPE, ptr, ...)                                        \
@@ -193,11 +218,12 @@ __device__ __forceinline__ void sp_store_vec(void* base, int32_t dt, int64_t off
     case SP_I32: {
       int32_t* p = (int32_t*)base + off;
       if constexpr (N == 4) {
-        SP_VST(sp_i32x4u, p, {(int32_t)src[0], (int32_t)src[1], (int32_t)src[2], (int32_t)src[3]});
+        SP_VST(sp_i32x4u, p, {sp_to_int<int32_t>(src[0]), sp_to_int<int32_t>(src[1]), sp_to_int<int32_t>(src[2]),
+                              sp_to_int<int32_t>(src[3])});
       } else if constexpr (N == 2) {
-        *(sp_i32x2u*)p = sp_i32x2{(int32_t)src[0], (int32_t)src[1]};
+        *(sp_i32x2u*)p = sp_i32x2{sp_to_int<int32_t>(src[0]), sp_to_int<int32_t>(src[1])};
       } else {
-        p[0] = (int32_t)src[0];
+        p[0] = sp_to_int<int32_t>(src[0]);
       }
     } break;
     case SP_I64: {
@@ -205,9 +231,9 @@ __device__ __forceinline__ void sp_store_vec(void* base, int32_t dt, int64_t off
 #pragma unroll
       for (int j = 0; j < N; j += 2) {
         if constexpr (N >= 2) {
-          SP_VST(sp_i64x2u, p + j, {(int64_t)src[j], (int64_t)src[j + 1]});
+          SP_VST(sp_i64x2u, p + j, {sp_to_int<int64_t>(src[j]), sp_to_int<int64_t>(src[j + 1])});
         } else {
-          p[0] = (int64_t)src[0];
+          p[0] = sp_to_int<int64_t>(src[0]);
         }
       }
     } break;
@@ -224,7 +250,7 @@ __device__ __forceinline__ void sp_store_vec(void* base, int32_t dt, int64_t off
     default: {  // SP_U8
       uint8_t* p = (uint8_t*)base + off;
 #pragma unroll
-      for (int j = 0; j < N; ++j) p[j] = (uint8_t)(int64_t)src[j];
+      for (int j = 0; j < N; ++j) p[j] = (uint8_t)sp_to_int<int32_t>(src[j]);
     } break;
   }
 }
@@ -271,9 +297,11 @@ struct sp_math<float> {
   static __device__ __forceinline__ T ceil_(T a) { return ceilf(a); }
   static __device__ __forceinline__ T abs_(T a) { return fabsf(a); }
   static __device__ __forceinline__ bool isnan_(T a) { return a != a; }
+  static __device__ __forceinline__ T recip_(T a) { return 1.0f / a; }
   static __device__ __forceinline__ T to_f32(T a) { return a; }
-  static __device__ __forceinline__ T to_i32(T a) { return (T)(int32_t)a; }
-  static __device__ __forceinline__ T to_i64(T a) { return (T)(int64_t)a; }
+  static __device__ __forceinline__ T to_i32(T a) { return (T)sp_f2i32(a); }
+  static __device__ __forceinline__ T to_i64(T a) { return (T)sp_f2i64(a); }
+  static __device__ __forceinline__ T to_u8(T a) { return (T)(uint8_t)sp_f2i32(a); }
 };
 
 template <>
@@ -313,24 +341,28 @@ struct sp_math<double> {
   static __device__ __forceinline__ T ceil_(T a) { return ceil(a); }
   static __device__ __forceinline__ T abs_(T a) { return fabs(a); }
   static __device__ __forceinline__ bool isnan_(T a) { return a != a; }
+  static __device__ __forceinline__ T recip_(T a) { return 1.0 / a; }
   static __device__ __forceinline__ T to_f32(T a) { return (T)(float)a; }
-  static __device__ __forceinline__ T to_i32(T a) { return (T)(int32_t)a; }
-  static __device__ __forceinline__ T to_i64(T a) { return (T)(int64_t)a; }
+  static __device__ __forceinline__ T to_i32(T a) { return (T)sp_f2i32(a); }
+  static __device__ __forceinline__ T to_i64(T a) { return (T)sp_f2i64(a); }
+  static __device__ __forceinline__ T to_u8(T a) { return (T)(uint8_t)sp_f2i32(a); }
 };
 
 template <>
 struct sp_math<int64_t> {
   using T = int64_t;
+  // (b == -1: a / b and a % b overflow for INT64_MIN; NumPy gives the wrapped -a and 0)
   static __device__ __forceinline__ T floordiv(T a, T b) {
     if (b == 0) return 0;  // numpy: 0 with a RuntimeWarning
+    if (b == -1) return (T)(0ULL - (uint64_t)a);
     T q = a / b;
     if ((a % b != 0) && ((a < 0) != (b < 0))) q -= 1;
     return q;
   }
   static __device__ __forceinline__ T div(T a, T b) { return floordiv(a, b); }
-  static __device__ __forceinline__ T fmod_(T a, T b) { return b == 0 ? 0 : a % b; }
+  static __device__ __forceinline__ T fmod_(T a, T b) { return (b == 0 || b == -1) ? 0 : a % b; }
   static __device__ __forceinline__ T mod(T a, T b) {
-    if (b == 0) return 0;
+    if (b == 0 || b == -1) return 0;
     T r = a % b;
     if (r != 0 && ((r < 0) != (b < 0))) r += b;
     return r;
@@ -352,11 +384,14 @@ struct sp_math<int64_t> {
   static __device__ __forceinline__ T normcdf_(T a) { return (T)(0.5 * erfc(-(double)a * 0.70710678118654752440)); }
   static __device__ __forceinline__ T floor_(T a) { return a; }
   static __device__ __forceinline__ T ceil_(T a) { return a; }
-  static __device__ __forceinline__ T abs_(T a) { return a < 0 ? -a : a; }
+  static __device__ __forceinline__ T abs_(T a) { return a < 0 ? (T)(0ULL - (uint64_t)a) : a; }  // |INT64_MIN| wraps
   static __device__ __forceinline__ bool isnan_(T) { return false; }
+  // np.reciprocal of an integer: 1.0 / a truncated, i.e. 1 / a for a != 0, and x86's INT64_MIN for 1.0 / 0 = inf
+  static __device__ __forceinline__ T recip_(T a) { return a == 0 ? (T)INT64_MIN : ((a == 1 || a == -1) ? a : 0); }
   static __device__ __forceinline__ T to_f32(T a) { return (T)(float)a; }
   static __device__ __forceinline__ T to_i32(T a) { return (T)(int32_t)a; }
   static __device__ __forceinline__ T to_i64(T a) { return a; }
+  static __device__ __forceinline__ T to_u8(T a) { return (T)(uint8_t)a; }
 };
 
 template <typename T>
@@ -611,8 +646,8 @@ __device__ __forceinline__ void sp_step(const sp_program& p, const sp_instr I, c
     case SP_OP_SQUARE: SP_EACH(av * av); break;
     case SP_OP_EXP: SP_EACH(M::exp_(av)); break;
     case SP_OP_LOG: SP_EACH(M::log_(av)); break;
-    case SP_OP_RECIP: SP_EACH(M::div((T)1, av)); break;
-    case SP_OP_SIGN: SP_EACH((T)((av > (T)0) - (av < (T)0))); break;
+    case SP_OP_RECIP: SP_EACH(M::recip_(av)); break;
+    case SP_OP_SIGN: SP_EACH(M::isnan_(av) ? av : (T)((av > (T)0) - (av < (T)0))); break;
     case SP_OP_FLOOR: SP_EACH(M::floor_(av)); break;
     case SP_OP_CEIL: SP_EACH(M::ceil_(av)); break;
     case SP_OP_TANH: SP_EACH(M::tanh_(av)); break;
@@ -629,7 +664,7 @@ __device__ __forceinline__ void sp_step(const sp_program& p, const sp_instr I, c
     case SP_OP_TO_I32: SP_EACH(M::to_i32(av)); break;
     case SP_OP_TO_I64: SP_EACH(M::to_i64(av)); break;
     case SP_OP_TO_BOOL: SP_EACH((T)(av != (T)0)); break;
-    case SP_OP_TO_U8: SP_EACH((T)(uint8_t)(int64_t)av); break;
+    case SP_OP_TO_U8: SP_EACH(M::to_u8(av)); break;
     case SP_OP_ADDC: { const T cv = sp_const<T>(p, I.a); SP_EACH(bv + cv); } break;
     case SP_OP_SUBC: { const T cv = sp_const<T>(p, I.a); SP_EACH(bv - cv); } break;
     case SP_OP_RSUBC: { const T cv = sp_const<T>(p, I.a); SP_EACH(cv - bv); } break;

@@ -322,9 +322,11 @@ __device__ __forceinline__ T sp_apply_reducer(int r, T old, T upd) {
   }
 }
 
-// T = arithmetic type of the destination tile (float / double / int64 for all
-// integer + bool tiles).  V consecutive elements of the innermost box
-// dimension per thread (contiguous in both tile and update).
+// T = the type NumPy computes reducer(old, update) in (sp_merge_class): float / double, or int64 for two integer /
+// bool operands -- wider than their promoted type, which the store's wrap to the tile's width makes invisible except
+// for a bool tile, whose value is the reduced one wrapped to the update's width, then tested against 0.  The result
+// (and a replaced cell's update) is stored with the astype rules of sp_store_vec.  V consecutive elements of the
+// innermost box dimension per thread (contiguous in both tile and update).
 template <typename T, int V>
 __global__ __launch_bounds__(SP_BLOCK) void sp_update_kernel(void* __restrict__ dst,
                                                              const void* __restrict__ src,
@@ -367,12 +369,30 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_update_kernel(void* __restrict__ 
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) res[v] = m[v] ? sp_apply_reducer<T>(u.reducer, old[v], upd[v]) : upd[v];
+    if constexpr (sp_is_integral<T>::value) {
+      // bool tile: NumPy reduced in the update's dtype (True + uint8 255 is 0 there, so False)
+      if (u.dst_dtype == SP_BOOL && (u.src_dtype == SP_U8 || u.src_dtype == SP_I32)) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) res[v] = u.src_dtype == SP_U8 ? (T)(uint8_t)res[v] : (T)(int32_t)res[v];
+      }
+    }
     sp_store_vec<T, V>(dst, u.dst_dtype, off, res);
     if (mask) {
 #pragma unroll
       for (int v = 0; v < V; ++v) mask[off + v] = 1;
     }
   }
+}
+
+// the type NumPy's reducer(old, update) computes in (tile.pyx:263-279: reduce, then cast to the tile's dtype):
+// float64 with a float64 operand or a float32 one next to int32 / int64; float32 for float32 next to float32, uint8 or
+// bool; int64 (standing in for the integer promotion) for two integer / bool operands
+static int sp_merge_class(int32_t dst, int32_t src) {
+  const bool wide_int_d = dst == SP_I32 || dst == SP_I64, wide_int_s = src == SP_I32 || src == SP_I64;
+  if (dst == SP_F64 || src == SP_F64) return SP_F64;
+  if (dst == SP_F32) return wide_int_s ? SP_F64 : SP_F32;
+  if (src == SP_F32) return wide_int_d ? SP_F64 : SP_F32;
+  return SP_I64;
 }
 
 template <typename T>
@@ -434,7 +454,7 @@ extern "C" int sp_update(void* d_dst, int32_t dst_dtype, const int64_t* dst_shap
   }
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  switch (dst_dtype) {
+  switch (sp_merge_class(dst_dtype, src_dtype)) {
     case SP_F32: return sp_update_launch<float>(d_dst, d_src, d_mask, u, n, st);
     case SP_F64: return sp_update_launch<double>(d_dst, d_src, d_mask, u, n, st);
     default: return sp_update_launch<int64_t>(d_dst, d_src, d_mask, u, n, st);
