@@ -8,6 +8,7 @@ the C-ABI's too -- no torch on this path).  Constructing it without a GPU or wit
 built library raises: there is no CPU fallback in the product path.
 """
 import collections
+import contextlib
 import os
 import time
 
@@ -41,21 +42,84 @@ def _content_stamp(view):
   return (view.shape, view.dtype.str, _digest(memoryview(view).cast('B')))
 
 
-class _FixedPoints(object):
-  def __init__(self, backend):
-    self.backend = backend
+def _same_view(a, b):
+  return a.shape == b.shape and a.strides == b.strides and a.dtype == b.dtype and a.data_ptr() == b.data_ptr()
 
-  def __enter__(self):
-    self.outer = self.backend._fixed_points
-    if self.outer is None:
-      self.backend._fixed_points = {}
-      self.backend._fit_labels = collections.OrderedDict()
-    return self
 
-  def __exit__(self, *exc):
-    self.backend._fixed_points = self.outer
-    if self.outer is None:
-      self.backend._fit_labels = None
+class _Fit(object):
+  """What the backend knows inside `with be.fixed_points():` (one k-means fit) -- `points`: what the kernels derive
+  from a point tile alone; `labels`: {address of a label tile: (the tile, the int64 labels it was cast from or None,
+  their np.bincount or None)}, the last few entries only, each holding its arrays alive (an address cannot be re-used
+  for something else while its entry is there)."""
+
+  def __init__(self):
+    self.points, self.labels = {}, collections.OrderedDict()
+
+  def prepared_for(self, points):
+    """The bf16 images of a (large fp32) point tile: made on their first use and kept to the end of the fit."""
+    if points.dtype != np.float32 or points.shape[0] < 1024:
+      return None
+    key = (points.data_ptr(), tuple(points.shape), tuple(points.strides))
+    prepared = self.points.get(key)
+    if prepared is None:
+      if len(self.points) >= 64:      # (points that are re-made every iteration: keep nothing of them)
+        self.points.clear()
+      prepared = self.points[key] = (kernels.prepare_points(points), points)     # (the tile stays alive)
+    return prepared[0]
+
+  def note(self, tile_, origin=None, counts=None):
+    key = tile_.data_ptr()
+    old = self.labels.pop(key, None)
+    if old is not None and _same_view(old[0], tile_):
+      origin = origin if origin is not None else old[1]
+      counts = counts if counts is not None else old[2]
+    self.labels[key] = (tile_, origin, counts)
+    # an iteration notes two tiles per worker (the int64 labels and their float32 image): two iterations' worth stay
+    from . import context
+    cap = 4 * (context.get().num_workers if context.initialized() else 1) + 4
+    while len(self.labels) > cap:
+      self.labels.popitem(last=False)
+
+  def known(self, labels):
+    """(int64 labels, their counts or None) of a label tile this fit produced, or (None, None)."""
+    if not isinstance(labels, D.DevArray):
+      return None, None
+    hit = self.labels.get(labels.data_ptr())
+    if hit is None or not _same_view(hit[0], labels):
+      return None, None
+    tile_, origin, counts = hit
+    if origin is None:
+      return (tile_ if tile_.dtype == np.int64 else None), counts
+    # counts noted under the origin's own entry (segment_sum sees the int64 array) count for the cast tile too
+    if counts is None:
+      o = self.labels.get(origin.data_ptr())
+      counts = o[2] if o is not None and _same_view(o[0], origin) else None
+    return origin, counts
+
+  def take_counts(self, labels):
+    """The counts this fit's segment_sum noted for these labels, handed over ONCE (the caller owns the array: a
+    target tile adopts it and may add to it in place)."""
+    origin, counts = self.known(labels)
+    if counts is None:
+      return None
+    for t in (labels, origin):
+      if t is not None:
+        e = self.labels.get(t.data_ptr())
+        if e is not None and e[2] is counts:
+          self.labels[t.data_ptr()] = (e[0], e[1], None)
+    return counts
+
+  def wrote(self, dst, ul, lr, src, reducer):
+    """update_box has just merged `src` into dst[ul:lr]."""
+    if (reducer is None and dst.dtype == np.float32 and src.dtype == np.int64 and tuple(src.shape) == tuple(dst.shape)
+        and tuple(lr) == tuple(dst.shape) and not any(ul) and src.data_ptr() in self.labels
+        and _same_view(self.labels[src.data_ptr()][0], src)):
+      # the int64 labels of a fit's assignment written over a whole float32 target tile (map2 targets take the
+      # points' dtype, map.py:317-318): remember which labels these floats ARE -- exact, nearest_center registers
+      # labels below 2^24 only -- so that the joins that read the target back need not convert them again
+      self.note(dst, origin=src)
+    else:
+      self.labels.pop(dst.data_ptr(), None)        # anything else written into a known label tile: forget it
 
 
 class _HostCopyLater(object):
@@ -88,6 +152,141 @@ class _HostCopyLater(object):
       pass
 
 
+class _HostCopies(object):
+  """The deferred device -> host copies of to_numpy_later: a side stream (made on first use) and the pinned landing
+  buffers, which are kept (hipHostMalloc maps memory, hipHostFree waits for the device) in free lists by size."""
+
+  def __init__(self):
+    self.stream, self.free = None, {}
+
+  def later(self, t):
+    ready = D.Event().record()
+    side = self.stream = self.stream or D.Stream()
+    side.wait_event(ready)
+    size = max(256, 1 << (max(t.nbytes, 1) - 1).bit_length())
+    free = self.free.setdefault(size, [])
+    if free:
+      host = free.pop()
+    else:
+      host = ctypes.c_void_p()
+      _hip.check(_hip.lib().sp_pinned_alloc(size, ctypes.byref(host)))
+    _hip.check(_hip.lib().sp_copy_d2h_async(host, ctypes.c_void_p(t.data_ptr()), t.nbytes, side.ptr))
+    return _HostCopyLater(t, host, free, D.Event().record(side))
+
+  def release(self):
+    for free in self.free.values():
+      while free:
+        _hip.lib().sp_pinned_free(free.pop())
+
+
+# What one fused launch is made of.  `operands` are the tensors the program reads -- in the table of lowered programs:
+# their positions among the operator tree's variables; red_op and the (outer, reduced, inner) split of the index space
+# belong to a map -> reduce and are None for a map.
+_Recipe = collections.namedtuple('_Recipe', 'prog operands shape dtype red_op O A I', defaults=(None,) * 4)
+
+
+class _Lowered(collections.OrderedDict):
+  """Lowered programs of fused operator trees seen before: (operator structure, operand types, tile shape) -> _Recipe
+  (see key).  A hit skips type inference and code emission, not the launch.  The last 512 are kept."""
+  hits = 0
+
+  @staticmethod
+  def structure(op):
+    """(structure, variable names in order of appearance, reads the tile's position?) of an operator tree made of
+    registered operators only -- None if it calls anything that is TRACED (a user's function: what it computes may
+    depend on values it closes over, which no key can see).  Remembered on the operator object: trees of optimised
+    DAGs answered from the plan table (expr/plan.py) are shared between evaluations."""
+    memo = getattr(op, '_lowering_structure', False)
+    if memo is not False:
+      return memo
+    names, positional = [], [False]
+
+    def walk(o):
+      if isinstance(o, LocalInput):
+        if o.idx in ('extent', 'axis'):
+          if o.idx == 'extent':
+            positional[0] = True
+          return o.idx
+        if o.idx not in names:
+          names.append(o.idx)
+        return names.index(o.idx)
+      if not isinstance(o, FnCallExpr) or (o.fn not in lower.MAP_RULES and o.fn not in lower.REDUCE_RULES):
+        raise lower.NotLowerable('traced')
+      if getattr(o.fn, '_sp_random', None) is not None or getattr(o.fn, '_sp_tile_fn', False):
+        raise lower.NotLowerable('not a kernel')
+      kw = ()
+      if o.kw:
+        kw = tuple(sorted((k, v if isinstance(v, (bool, int, float, str, type(None))) else np.dtype(v).str)
+                          for k, v in o.kw.items()))
+      if isinstance(o, LocalMapLocationExpr):
+        positional[0] = True
+      return (type(o).__name__, id(o.fn), kw, tuple([walk(d) for d in o.deps]))
+    try:
+      memo = (walk(op), tuple(names), positional[0])
+      hash(memo)
+    except (lower.NotLowerable, TypeError):
+      memo = None
+    try:
+      op._lowering_structure = memo
+    except AttributeError:
+      pass
+    return memo
+
+  def key(self, op, inputs, ex, extra):
+    """What a program lowered for evaluate_map / evaluate_reduce(op, inputs, ex) depends on, or None when it cannot be
+    replayed from the table."""
+    st = getattr(op, '_lowering_structure', False)
+    if st is False:
+      st = self.structure(op)
+    if st is None:
+      return None
+    structure, names, positional = st
+    described, ptrs = [], []
+    for n in names:
+      v = inputs.get(n)
+      t = type(v)
+      if t is D.DevArray:
+        # (address: two names may read the same bytes -- the emitter then loads them once -- and alignment decides
+        #  the kernel's vector width; both are functions of the low bits and of equality between operands)
+        p = v.data_ptr()
+        described.append((v.dtype, v.shape, v.strides, p & 15, ptrs.index(p) if p in ptrs else len(ptrs)))
+        ptrs.append(p)
+      elif t in (bool, int, float):
+        described.append((t, v))
+      elif isinstance(v, np.generic):
+        described.append((v.dtype.str, v.item()))
+      else:
+        return None          # NumPy operands (uploaded through the driver-array cache), empty / sparse / masked tiles
+    where = (ex.ul, ex.lr, ex.array_shape) if positional else ex.shape
+    return (structure, tuple(described), where, extra)
+
+  def remember(self, key, recipe, inputs, op):
+    """Keep the program of a launch whose operands were exactly (some of) the device tiles handed in; operands are
+    remembered by their POSITION among the operator tree's variables (two trees of one structure name them apart)."""
+    names = op._lowering_structure[1]
+    by_id = {id(inputs[n]): i for i, n in enumerate(names) if type(inputs.get(n)) is D.DevArray}
+    order = [by_id.get(id(t)) for t in recipe.operands]
+    if None in order:
+      return              # a carved sub-expression, a dense copy of a view, an uploaded operand: not replayable as is
+    self[key] = recipe._replace(operands=order)
+    while len(self) > 512:
+      self.popitem(last=False)
+
+  def replay(self, recipe, inputs, op):
+    """The one launch of a remembered program on the tiles of this evaluation."""
+    prog, order, shape, dtype, red_op, O, A, I = recipe
+    names = op._lowering_structure[1]
+    tensors = [inputs[names[i]] for i in order]
+    self.hits += 1
+    if red_op is None:
+      out = D.empty(shape, dtype)
+      kernels.map_fused(prog, tensors, out)
+      return out
+    out = D.empty((O * I,), dtype)
+    kernels.reduce(prog, tensors, red_op, O, A, I, out)
+    return out.reshape(shape)
+
+
 def _no_copy(t):
   raise lower.NotLowerable('an operand the kernels cannot address in place')
 
@@ -101,25 +300,7 @@ class HipBackend(object):
     if lib.sp_device_count(ctypes.byref(count)) != 0 or count.value < 1:
       raise _hip.HipError('the HIP tile backend needs an AMD GPU (no HIP device is visible); '
                           'there is no CPU fallback')
-    self.device = 'hip'
-    self._np_cache = collections.OrderedDict()   # bounded: iterative drivers pass a new array every step
-    self._side_copies, self._pinned_free = None, {}     # to_numpy_later
-    self._fixed_points = None                            # fixed_points()
-    # inside a fit: what is known about label tiles -- {address of a tile: (the tile, the int64 labels it was cast
-    # from or None, their np.bincount or None)}; the last few entries only, each holding its arrays alive (an
-    # address cannot be re-used for something else while its entry is there)
-    self._fit_labels = None
-    self.launches = 0
-    self.gemms = 0            # gemm_into launches (the K-split tests count them)
-    self.host_round_trips = 0  # local functions that had to run on host copies of their tiles (call_local_fn)
-    self._warned_host = set()
-    self.gemm_events = None   # set to [] to record (start, stop) HIP events around every GEMM launch
-    self._rng_seed = (int(time.time() * 100000) + os.getpid()) & (2**63 - 1)   # srandom.py:23-35: from the clock
-    self._rng_offset = 0
-    # lowered programs of fused operator trees seen before: (operator structure, operand types, tile shape) ->
-    # program + operand order (see _lowering_key); a hit skips type inference and code emission, not the launch
-    self._lowered = collections.OrderedDict()
-    self.lowering_hits = 0
+    self._init_state()
     lower.warm_result_dtypes()
     # the code objects that travel with the tree (csrc/jit_seed) are loaded while the host builds its first
     # expressions: ctypes drops the GIL for the call, a seeded program then starts specialised at once
@@ -130,6 +311,26 @@ class HipBackend(object):
       t = threading.Thread(target=lib.sp_jit_preload, args=(dev.value,), daemon=True, name='sp_jit_preload')
       t.start()
       atexit.register(t.join)     # (never inside hipModuleLoadData when the runtime is torn down)
+
+  def _init_state(self, device='hip', rng_seed=None):
+    """Every attribute of a backend (jit_seed's backend without a device has the same ones)."""
+    self.device = device
+    self._np_cache = collections.OrderedDict()   # bounded: iterative drivers pass a new array every step
+    self._host_copies = _HostCopies()            # to_numpy_later
+    self._fit = None                             # a _Fit inside fixed_points()
+    self._probe_stream = None                    # liveness_probe
+    self.launches = 0
+    self.gemms = 0            # gemm_into launches (the K-split tests count them)
+    self.host_round_trips = 0  # local functions that had to run on host copies of their tiles (call_local_fn)
+    self._warned_host = set()
+    self.gemm_events = None   # set to [] to record (start, stop) HIP events around every GEMM launch
+    if rng_seed is None:      # srandom.py:23-35: from the clock
+      rng_seed = (int(time.time() * 100000) + os.getpid()) & (2**63 - 1)
+    self._rng_seed, self._rng_offset = rng_seed, 0
+    self._lowered = self._lowered_type()
+
+  _lowered_type = _Lowered      # (jit_seed's backend has a table that keeps nothing)
+  lowering_hits = property(lambda self: self._lowered.hits)
 
   # -- memory -------------------------------------------------------------------
   def empty(self, shape, dtype):
@@ -153,28 +354,11 @@ class HipBackend(object):
     HAS RUN -- without making the host wait now: the copy is put on a side stream behind an event into a pinned
     buffer, the compute stream goes on (sp_copy_d2h_async).  For values a driver only CHECKS (the cluster counts of
     a k-means iteration), one iteration later."""
-    t = self.contiguous(t)
-    ready = D.Event().record()
-    if self._side_copies is None:
-      self._side_copies = D.Stream()
-    side = self._side_copies
-    side.wait_event(ready)
-    # pinned landing buffers are kept (hipHostMalloc maps memory, hipHostFree waits for the device): free lists by size
-    size = max(256, 1 << (max(t.nbytes, 1) - 1).bit_length())
-    free = self._pinned_free.setdefault(size, [])
-    if free:
-      host = free.pop()
-    else:
-      host = ctypes.c_void_p()
-      _hip.check(_hip.lib().sp_pinned_alloc(size, ctypes.byref(host)))
-    _hip.check(_hip.lib().sp_copy_d2h_async(host, ctypes.c_void_p(t.data_ptr()), t.nbytes, side.ptr))
-    return _HostCopyLater(t, host, free, D.Event().record(side))
+    return self._host_copies.later(self.contiguous(t))
 
   def release_pinned(self):
     """Give the pooled landing buffers of to_numpy_later back (waits for the device: hipHostFree)."""
-    for free in self._pinned_free.values():
-      while free:
-        _hip.lib().sp_pinned_free(free.pop())
+    self._host_copies.release()
 
   def dtype_of(self, t):
     if isinstance(t, sparse_mod.CsrTile):
@@ -209,55 +393,6 @@ class HipBackend(object):
       return t
     v = lower.cast(lower.V('tensor', dtype=self.dtype_of(t), shape=tuple(t.shape), tensor=t), dtype)
     return self._run_map(v, tuple(t.shape))
-
-  def _note_labels(self, tile_, origin=None, counts=None):
-    known = self._fit_labels
-    key = tile_.data_ptr()
-    old = known.pop(key, None)
-    if old is not None and self._same_view(old[0], tile_):
-      origin = origin if origin is not None else old[1]
-      counts = counts if counts is not None else old[2]
-    known[key] = (tile_, origin, counts)
-    # an iteration notes two tiles per worker (the int64 labels and their float32 image): two iterations' worth stay
-    from . import context
-    cap = 4 * (context.get().num_workers if context.initialized() else 1) + 4
-    while len(known) > cap:
-      known.popitem(last=False)
-
-  @staticmethod
-  def _same_view(a, b):
-    return a.shape == b.shape and a.strides == b.strides and a.dtype == b.dtype and a.data_ptr() == b.data_ptr()
-
-  def _known_labels(self, labels):
-    """(int64 labels, their counts or None) of a label tile this fit produced, or (None, None)."""
-    known = self._fit_labels
-    if known is None or not isinstance(labels, D.DevArray):
-      return None, None
-    hit = known.get(labels.data_ptr())
-    if hit is None or not self._same_view(hit[0], labels):
-      return None, None
-    tile_, origin, counts = hit
-    if origin is None:
-      return (tile_ if tile_.dtype == np.int64 else None), counts
-    # counts noted under the origin's own entry (segment_sum sees the int64 array) count for the cast tile too
-    if counts is None:
-      o = known.get(origin.data_ptr())
-      counts = o[2] if o is not None and self._same_view(o[0], origin) else None
-    return origin, counts
-
-  def _take_counts(self, labels):
-    """The counts this fit's segment_sum noted for these labels, handed over ONCE (the caller owns the array: a
-    target tile adopts it and may add to it in place)."""
-    origin, counts = self._known_labels(labels)
-    if counts is None:
-      return None
-    known = self._fit_labels
-    for t in (labels, origin):
-      if t is not None:
-        e = known.get(t.data_ptr())
-        if e is not None and e[2] is counts:
-          known[t.data_ptr()] = (e[0], e[1], None)
-    return counts
 
   def cached_numpy(self, arr, slices):
     """A (slice of a) driver-side NumPy operand in HBM (the reference pickles it into every RunKernelReq,
@@ -332,17 +467,8 @@ class HipBackend(object):
     if not dst.is_contiguous():
       raise _hip.HipError('update target must be a dense tile')
     kernels.update(dst, ul, lr, src, self.reducer_name(reducer), mask_mode, mask)
-    known = self._fit_labels
-    if known is not None:
-      if (reducer is None and dst.dtype == np.float32 and src.dtype == np.int64 and tuple(src.shape) == tuple(dst.shape)
-          and tuple(lr) == tuple(dst.shape) and not any(ul) and src.data_ptr() in known
-          and self._same_view(known[src.data_ptr()][0], src)):
-        # the int64 labels of a fit's assignment written over a whole float32 target tile (map2 targets take the
-        # points' dtype, map.py:317-318): remember which labels these floats ARE -- exact, nearest_center registers
-        # labels below 2^24 only -- so that the joins that read the target back need not convert them again
-        self._note_labels(dst, origin=src)
-      elif dst.data_ptr() in known:
-        known.pop(dst.data_ptr(), None)        # anything else written into a known label tile: forget it
+    if self._fit is not None:
+      self._fit.wrote(dst, ul, lr, src, reducer)
 
   def mask_all_set(self, mask, subslice):
     return bool(self.evaluate_reduce_tensor(mask[subslice], 'AND').item())
@@ -410,93 +536,23 @@ class HipBackend(object):
         if not self._carve(root):
           raise
 
-  def _run_map(self, root, out_shape, out_dtype=None):
+  def _launch_map(self, root, out_shape, out_dtype=None):
+    """(result, the _Recipe of the launch that wrote it -- None if nothing was launched: an empty tile)."""
     prog, tensors, out_dtype = self._emit_map(root, out_shape, out_dtype)
     out = self.empty(out_shape, out_dtype)
-    if out.numel():
-      self.launches += 1
-      kernels.map_fused(prog, tensors, out)
-      self._last_map = (prog, tensors, tuple(out.shape), out_dtype)      # (evaluate_map may remember it)
-    return out
+    if not out.numel():
+      return out, None
+    self.launches += 1
+    kernels.map_fused(prog, tensors, out)
+    return out, _Recipe(prog, tensors, tuple(out.shape), out_dtype)
 
-  # -- lowered programs of operator trees seen before ---------------------------------------------------------
-  def _op_structure(self, op):
-    """(structure, variable names in order of appearance, reads the tile's position?) of an operator tree made of
-    registered operators only -- None if it calls anything that is TRACED (a user's function: what it computes may
-    depend on values it closes over, which no key can see).  Remembered on the operator object: trees of optimised
-    DAGs answered from the plan table (expr/plan.py) are shared between evaluations."""
-    memo = getattr(op, '_lowering_structure', False)
-    if memo is not False:
-      return memo
-    names, positional = [], [False]
+  def _run_map(self, root, out_shape, out_dtype=None):
+    return self._launch_map(root, out_shape, out_dtype)[0]
 
-    def walk(o):
-      if isinstance(o, LocalInput):
-        if o.idx in ('extent', 'axis'):
-          if o.idx == 'extent':
-            positional[0] = True
-          return o.idx
-        if o.idx not in names:
-          names.append(o.idx)
-        return names.index(o.idx)
-      if not isinstance(o, FnCallExpr) or (o.fn not in lower.MAP_RULES and o.fn not in lower.REDUCE_RULES):
-        raise lower.NotLowerable('traced')
-      if getattr(o.fn, '_sp_random', None) is not None or getattr(o.fn, '_sp_tile_fn', False):
-        raise lower.NotLowerable('not a kernel')
-      kw = ()
-      if o.kw:
-        kw = tuple(sorted((k, v if isinstance(v, (bool, int, float, str, type(None))) else np.dtype(v).str)
-                          for k, v in o.kw.items()))
-      if isinstance(o, LocalMapLocationExpr):
-        positional[0] = True
-      return (type(o).__name__, id(o.fn), kw, tuple([walk(d) for d in o.deps]))
-    try:
-      memo = (walk(op), tuple(names), positional[0])
-      hash(memo)
-    except (lower.NotLowerable, TypeError):
-      memo = None
-    try:
-      op._lowering_structure = memo
-    except AttributeError:
-      pass
-    return memo
-
-  def _lowering_key(self, op, inputs, ex, extra):
-    st = self._op_structure(op)
-    if st is None:
-      return None
-    structure, names, positional = st
-    described, ptrs = [], []
-    for n in names:
-      v = inputs.get(n)
-      t = type(v)
-      if t is D.DevArray:
-        # (address: two names may read the same bytes -- the emitter then loads them once -- and alignment decides
-        #  the kernel's vector width; both are functions of the low bits and of equality between operands)
-        p = v.data_ptr()
-        described.append((v.dtype, v.shape, v.strides, p & 15, ptrs.index(p) if p in ptrs else len(ptrs)))
-        ptrs.append(p)
-      elif t in (bool, int, float):
-        described.append((t, v))
-      elif isinstance(v, np.generic):
-        described.append((v.dtype.str, v.item()))
-      else:
-        return None          # NumPy operands (uploaded through the driver-array cache), empty / sparse / masked tiles
-    where = (ex.ul, ex.lr, ex.array_shape) if positional else ex.shape
-    return (structure, tuple(described), where, extra)
-
-  def _remember(self, key, launch, inputs, op):
-    """Keep the program of a launch whose operands were exactly (some of) the device tiles handed in; operands are
-    remembered by their POSITION among the operator tree's variables (two trees of one structure name them apart)."""
-    prog, tensors, out_shape, out_dtype = launch[:4]
-    names = op._lowering_structure[1]
-    by_id = {id(inputs[n]): i for i, n in enumerate(names) if type(inputs.get(n)) is D.DevArray}
-    order = [by_id.get(id(t)) for t in tensors]
-    if None in order:
-      return              # a carved sub-expression, a dense copy of a view, an uploaded operand: not replayable as is
-    self._lowered[key] = (prog, order, out_shape, np.dtype(out_dtype)) + tuple(launch[4:])
-    while len(self._lowered) > 512:
-      self._lowered.popitem(last=False)
+  def _infer_map(self, op, inputs, ex):
+    """(lowered tree, shape of its result) of a local map over these tiles."""
+    root = lower.infer(op, inputs, ex, self.dtype_of)
+    return root, (root.shape if root.kind != 'const' else ex.shape)
 
   def seed_random(self, seed):
     self._rng_seed = int(seed) & (2**63 - 1)
@@ -513,33 +569,52 @@ class HipBackend(object):
       self._rng_offset += n + (n & 1)
     return out
 
+  def _not_one_kernel(self, op, inputs):
+    """Why evaluate_map(op, inputs, .) is not one fused kernel over the tiles handed in -- such an evaluation has no
+    place in the table of lowered programs -- or None."""
+    fn = getattr(op, 'fn', None)
+    if getattr(fn, '_sp_random', None) is not None:
+      return 'random'
+    if getattr(fn, '_sp_tile_fn', False):
+      return 'tile function'
+    if any(tile.is_sparse_blob(v) for v in inputs.values()):
+      return 'sparse'
+    return 'random below' if not getattr(op, '_no_random_below', False) and self._random_below(op) else None
+
+  def _random_below(self, op):
+    """Does the tree draw random numbers below its root?  (No: remembered on the tree; trees are not mutated.)"""
+    if not isinstance(op, FnCallExpr) or getattr(op, '_no_random_below', False):
+      return False
+    for d in op.deps:
+      if getattr(getattr(d, 'fn', None), '_sp_random', None) is not None or self._random_below(d):
+        return True
+    op._no_random_below = True
+    return False
+
   def evaluate_map(self, op, inputs, ex):
     """tile_mapper body: the fused map as ONE launch (map.py:74, local.py:115-127)."""
-    rnd = getattr(getattr(op, 'fn', None), '_sp_random', None)
-    if rnd is not None:
-      return self.random_tile(rnd[0], ex.shape, rnd[1], **(op.kw or {}))
-    if getattr(getattr(op, 'fn', None), '_sp_tile_fn', False):
-      return self._call_tile_fn(op, inputs, ex)
-    if any(tile.is_sparse_blob(v) for v in inputs.values()):
-      return self._evaluate_sparse_map(op, inputs, ex)
-    op, inputs = self._materialise_random(op, inputs, ex)
-    key = self._lowering_key(op, inputs, ex, None)
-    if key is not None:
-      hit = self._lowered.get(key)
-      if hit is not None:
-        prog, order, out_shape, out_dtype = hit
-        names = op._lowering_structure[1]
-        out = D.empty(out_shape, out_dtype)
-        self.launches += 1
-        self.lowering_hits += 1
-        kernels.map_fused(prog, [inputs[names[i]] for i in order], out)
-        return out
+    why = self._not_one_kernel(op, inputs)
+    if why is not None:
+      if why == 'random':
+        rnd = op.fn._sp_random
+        return self.random_tile(rnd[0], ex.shape, rnd[1], **(op.kw or {}))
+      if why == 'tile function':
+        return self._call_tile_fn(op, inputs, ex)
+      if why == 'sparse':
+        return self._evaluate_sparse_map(op, inputs, ex)
+      # random sources below the root are drawn here; what is left is one kernel over tiles and is keyed like any
+      # other (only here: prelower_map and map_result_meta may not draw, so they stop at the predicate)
+      op, inputs = self._materialise_random(op, inputs, ex)
+    key = self._lowered.key(op, inputs, ex, None)
+    hit = self._lowered.get(key) if key is not None else None
+    if hit is not None:
+      self.launches += 1
+      return self._lowered.replay(hit, inputs, op)
     try:
-      root = lower.infer(op, inputs, ex, self.dtype_of)
-      self._last_map = None
-      out = self._run_map(root, root.shape if root.kind != 'const' else ex.shape)
-      if key is not None and self._last_map is not None:
-        self._remember(key, self._last_map, inputs, op)
+      root, shape = self._infer_map(op, inputs, ex)
+      out, recipe = self._launch_map(root, shape)
+      if key is not None and recipe is not None:
+        self._lowered.remember(key, recipe, inputs, op)
       return out
     except ProgramTooLarge:
       return self._evaluate_split(op, inputs, ex)
@@ -553,23 +628,17 @@ class HipBackend(object):
     first evaluation finds its program like every later one does.  Only what can be replayed from the table is
     prepared -- device tiles and scalars in, one launch; anything else is left to evaluate_map.  Returns whether the
     table now answers this key."""
-    fn = getattr(op, 'fn', None)
-    if getattr(fn, '_sp_random', None) is not None or getattr(fn, '_sp_tile_fn', False):
-      return False
-    if any(tile.is_sparse_blob(v) for v in inputs.values()) or self._materialise_random_needed(op):
-      return False
-    key = self._lowering_key(op, inputs, ex, None)
+    key = None if self._not_one_kernel(op, inputs) else self._lowered.key(op, inputs, ex, None)
     if key is None:
       return False
     if key in self._lowered:
       return True
     try:
-      root = lower.infer(op, inputs, ex, self.dtype_of)
-      prog, tensors, out_dtype = self._emit_map(root, root.shape if root.kind != 'const' else ex.shape, None,
-                                                launches_allowed=False)
+      root, shape = self._infer_map(op, inputs, ex)
+      prog, tensors, out_dtype = self._emit_map(root, shape, None, launches_allowed=False)
     except (ProgramTooLarge, lower.NotLowerable):
       return False
-    self._remember(key, (prog, tensors, tuple(root.shape if root.kind != 'const' else ex.shape), out_dtype), inputs, op)
+    self._lowered.remember(key, _Recipe(prog, tensors, tuple(shape), out_dtype), inputs, op)
     return key in self._lowered
 
   def map_result_meta(self, op, inputs, ex):
@@ -577,34 +646,23 @@ class HipBackend(object):
     dtypes and shapes alone -- `inputs` may hold placeholders of tiles that live on other ranks -- or None when only
     running it can tell (sparse operands, whole-tile functions, a user function that cannot be traced).  The answer
     depends on nothing a rank holds alone, so every rank gets the same one."""
-    fn = getattr(op, 'fn', None)
-    rnd = getattr(fn, '_sp_random', None)
-    if rnd is not None:
-      return (np.dtype(rnd[1]), False)
-    if getattr(fn, '_sp_tile_fn', False) or self._op_structure(op) is None:
+    why = self._not_one_kernel(op, inputs)
+    if why == 'random':
+      return (np.dtype(op.fn._sp_random[1]), False)
+    if why is not None or self._lowered.structure(op) is None:
       return None          # (a user's function would have to be RUN to be traced: never for a derivation)
     described = {}
     for name, v in inputs.items():
-      if tile.is_sparse_blob(v) or isinstance(v, tile.MaskedBlob):
+      if isinstance(v, tile.MaskedBlob):
         return None
       if isinstance(v, (distarray.Absent, D.DevArray)):
         v = lower.V('tensor', dtype=v.dtype, shape=tuple(v.shape), tensor=None)
       described[name] = v
     try:
-      if self._materialise_random_needed(op):
-        return None
       root = lower.infer(op, described, ex, self.dtype_of)
       return (np.dtype(root.dtype), False) if root.dtype is not None else None
     except Exception:   # noqa: BLE001  (whatever stops the derivation stops it on every rank alike)
       return None
-
-  def _materialise_random_needed(self, op):
-    for d in getattr(op, 'deps', ()):
-      if getattr(getattr(d, 'fn', None), '_sp_random', None) is not None:
-        return True
-      if isinstance(d, FnCallExpr) and self._materialise_random_needed(d):
-        return True
-    return False
 
   # -- local functions that are not element-wise kernels ---------------------------------------------------------
   def _evaluate_eager(self, op, inputs, ex):
@@ -624,8 +682,7 @@ class HipBackend(object):
         raise lower.NotLowerable('cannot evaluate local expression %r' % (node,))
       if node is not op:
         try:
-          root = lower.infer(node, inputs, ex, self.dtype_of)
-          return self._run_map(root, root.shape if root.kind != 'const' else ex.shape)
+          return self._run_map(*self._infer_map(node, inputs, ex))
         except (lower.NotLowerable, ProgramTooLarge):
           pass
       return self.call_local_fn(node.fn, [ev(d) for d in node.deps], dict(node.kw or {}), node.fn_name())
@@ -684,47 +741,30 @@ class HipBackend(object):
     """Random sources fused INTO a tree (the reference's fusion does that despite @not_idempotent,
     because the marker is keyed by id() and the optimiser clones nodes: `(r - r).optimized()` draws
     twice there too) become tensor inputs, one fill per occurrence, like the reference's evaluation."""
-    if not isinstance(op, FnCallExpr) or getattr(op, '_no_random_below', False):
-      return op, inputs
-    new_deps, changed = [], False
+    inputs, new_deps = dict(inputs), []
     for i, d in enumerate(op.deps):
       rnd = getattr(getattr(d, 'fn', None), '_sp_random', None)
       if rnd is not None:
-        if not changed:
-          inputs = dict(inputs)
         name = '__random_%d_%d' % (id(op), i)
         inputs[name] = self.random_tile(rnd[0], ex.shape, rnd[1], **(d.kw or {}))
-        new_deps.append(LocalInput(idx=name))
-        changed = True
-      elif isinstance(d, FnCallExpr):
-        nd, inputs2 = self._materialise_random(d, inputs, ex)
-        if nd is not d:
-          changed = True
-          inputs = inputs2
-        new_deps.append(nd)
-      else:
-        new_deps.append(d)
-    if not changed:
-      op._no_random_below = True         # (operator trees are not mutated once built: remembered on the tree)
-      return op, inputs
+        d = LocalInput(idx=name)
+      elif self._random_below(d):
+        d, inputs = self._materialise_random(d, inputs, ex)
+      new_deps.append(d)
     return op.__class__(fn=op.fn, kw=op.kw, pretty_fn=op.pretty_fn, deps=new_deps), inputs
 
   def _evaluate_split(self, op, inputs, ex):
     """The tree does not fit one kernel: materialise its sub-expressions first."""
     if not isinstance(op, FnCallExpr):
       raise
-    new_deps = []
-    new_inputs = dict(inputs)
-    progressed = False
+    new_deps, new_inputs = [], dict(inputs)
     for i, d in enumerate(op.deps):
       if isinstance(d, FnCallExpr):
         name = '__split_%d_%d' % (id(op), i)
         new_inputs[name] = self.evaluate_map(d, inputs, ex)
-        new_deps.append(LocalInput(idx=name))
-        progressed = True
-      else:
-        new_deps.append(d)
-    if not progressed:
+        d = LocalInput(idx=name)
+      new_deps.append(d)
+    if len(new_inputs) == len(inputs):
       raise ProgramTooLarge('a single local function call does not fit one kernel')
     clone = op.__class__(fn=op.fn, kw=op.kw, pretty_fn=op.pretty_fn, deps=new_deps)
     root = lower.infer(clone, new_inputs, ex, self.dtype_of)
@@ -751,8 +791,7 @@ class HipBackend(object):
             int(np.prod(shape[axis + 1:], dtype=np.int64)))
 
   def _build_reduce(self, data, red_op, nat_dtype, shape, axis):
-    """The launch recipe of a fused map -> reduce over one tile: (prog, tensors, result shape, natural dtype,
-    red_op, O, A, I).  Nothing runs and nothing is allocated."""
+    """The _Recipe of a fused map -> reduce over one tile.  Nothing runs and nothing is allocated."""
     self._prepare(data)
     if data.kind in ('const', 'shape'):
       raise lower.NotLowerable('reduction over a constant')
@@ -770,16 +809,18 @@ class HipBackend(object):
     else:
       ax = axis if axis >= 0 else axis + len(full_shape)
       shape = full_shape[:ax] + full_shape[ax + 1:]
-    return (prog, tensors, shape, nat_dtype, red_op, O, A, I)
+    return _Recipe(prog, tensors, shape, nat_dtype, red_op, O, A, I)
+
+  def _launch_reduce(self, data, red_op, nat_dtype, shape, axis):
+    """(result, the _Recipe of the launch that wrote it)."""
+    r = self._build_reduce(data, red_op, nat_dtype, shape, axis)
+    out = self.empty((r.O * r.I,), r.dtype)
+    self.launches += 1
+    kernels.reduce(r.prog, r.operands, r.red_op, r.O, r.A, r.I, out)
+    return out.reshape(r.shape), r
 
   def _run_reduce(self, data, red_op, nat_dtype, shape, axis):
-    recipe = self._build_reduce(data, red_op, nat_dtype, shape, axis)
-    prog, tensors, shape, nat_dtype, red_op, O, A, I = recipe
-    out = self.empty((O * I,), nat_dtype)
-    self.launches += 1
-    kernels.reduce(prog, tensors, red_op, O, A, I, out)
-    self._last_reduce = recipe
-    return out.reshape(shape)
+    return self._launch_reduce(data, red_op, nat_dtype, shape, axis)[0]
 
   def prelower_reduce(self, op, inputs, ex, axis):
     """prelower_map for the local reduction of a ReduceExpr: the fused map -> reduce program of evaluate_reduce(op,
@@ -787,12 +828,10 @@ class HipBackend(object):
     that the first evaluation replays it like every later one, with the partials' workspace already at its size
     (`kernels.reduce_warm`)."""
     rule = lower.REDUCE_RULES.get(op.fn)
-    if rule is None or any(tile.is_sparse_blob(v) for v in inputs.values()):
-      return False
     data_deps = [d for d in op.deps if not (isinstance(d, LocalInput) and d.idx in ('extent', 'axis'))]
-    if len(data_deps) != 1 or self._materialise_random_needed(op):
+    if rule is None or len(data_deps) != 1 or self._not_one_kernel(op, inputs):
       return False
-    key = self._lowering_key(op, inputs, ex, ('reduce', axis))
+    key = self._lowered.key(op, inputs, ex, ('reduce', axis))
     if key is None:
       return False
     if key in self._lowered:
@@ -800,13 +839,12 @@ class HipBackend(object):
     try:
       data = lower.infer(data_deps[0], inputs, ex, self.dtype_of)
       red_op, data, nat = rule(data, axis, ex)
-      recipe = self._build_reduce(data, red_op, nat, ex.shape, axis)
+      r = self._build_reduce(data, red_op, nat, ex.shape, axis)
     except (ProgramTooLarge, lower.NotLowerable, _hip.HipError):
       return False
-    self._remember(key, recipe, inputs, op)
+    self._lowered.remember(key, r, inputs, op)
     if key in self._lowered:
-      prog, tensors, _, nat_dtype, red_op, O, A, I = recipe
-      kernels.reduce_warm(prog, tensors, red_op, O, A, I, nat_dtype)
+      kernels.reduce_warm(r.prog, r.operands, r.red_op, r.O, r.A, r.I, r.dtype)
     return key in self._lowered
 
   def evaluate_reduce(self, op, inputs, ex, axis):
@@ -828,27 +866,17 @@ class HipBackend(object):
       raise lower.NotLowerable('reduce over %d operands' % len(data_deps))
     if any(tile.is_sparse_blob(v) for v in inputs.values()):
       return self._evaluate_sparse_reduce(op, data_deps[0], inputs, ex, axis)
-    key = self._lowering_key(op, inputs, ex, ('reduce', axis))
-    if key is not None:
-      hit = self._lowered.get(key)
-      if hit is not None:
-        prog, order, shape, nat, red_op, O, A, I = hit
-        names = op._lowering_structure[1]
-        out = D.empty((O * I,), nat)
-        self.launches += 1
-        self.lowering_hits += 1
-        kernels.reduce(prog, [inputs[names[i]] for i in order], red_op, O, A, I, out)
-        return out.reshape(shape)
-    try:
-      data = lower.infer(data_deps[0], inputs, ex, self.dtype_of)
-    except ProgramTooLarge:
-      raise
+    key = self._lowered.key(op, inputs, ex, ('reduce', axis))
+    hit = self._lowered.get(key) if key is not None else None
+    if hit is not None:
+      self.launches += 1
+      return self._lowered.replay(hit, inputs, op)
+    data = lower.infer(data_deps[0], inputs, ex, self.dtype_of)
     red_op, data, nat = rule(data, axis, ex)
     try:
-      self._last_reduce = None
-      out = self._run_reduce(data, red_op, nat, ex.shape, axis)
-      if key is not None and self._last_reduce is not None:
-        self._remember(key, self._last_reduce, inputs, op)
+      out, recipe = self._launch_reduce(data, red_op, nat, ex.shape, axis)
+      if key is not None:
+        self._lowered.remember(key, recipe, inputs, op)
       return out
     except ProgramTooLarge:
       # materialise the map, then reduce the dense result
@@ -914,23 +942,12 @@ class HipBackend(object):
       return self.dot(a.reshape(a.shape[1]), b).reshape(1, b.shape[1])
     if a.dim() == 2 and b.dim() == 2 and a_dt == b_dt and a_dt in (np.float32, np.float64):
       # fp32 / fp64 MFMA GEMM (sp_gemm_f32 / sp_gemm_f64)
-      M, K = a.shape
-      N = b.shape[1]
-      c = self.empty((M, N), a_dt)
+      c = self.empty((a.shape[0], b.shape[1]), a_dt)
       if a.stride(1) != 1:
         a = self.copy(a)
       if b.stride(1) != 1:
         b = self.copy(b)
-      self.launches += 1
-      if self.gemm_events is not None:
-        e0, e1 = kernels.Event(), kernels.Event()
-        e0.record()
-        kernels.gemm_f32(a, b, c, accumulate=False)
-        e1.record()
-        self.gemm_events.append((e0, e1, M, N, K))
-      else:
-        kernels.gemm_f32(a, b, c, accumulate=False)
-      return c
+      return self._gemm(a, b, c)
     va = lower.V('tensor', dtype=a_dt, shape=tuple(a.shape), tensor=self.contiguous(a))
     vb = lower.V('tensor', dtype=b_dt, shape=tuple(b.shape), tensor=self.contiguous(b))
     if a.dim() == 2 and b.dim() == 1:      # (M,K).(K,) -> (M,): row kernels
@@ -952,20 +969,22 @@ class HipBackend(object):
       return self._run_reduce(prod, 'SUM', res_dt, (M, K, N), 1)
     raise lower.NotLowerable('dot of %d-d and %d-d operands' % (a.dim(), b.dim()))
 
+  def _gemm(self, a, b, c, accumulate=False):
+    """One sp_gemm launch, c (+)= a . b, between two events when `gemm_events` is a list."""
+    self.launches += 1
+    if self.gemm_events is None:
+      return kernels.gemm_f32(a, b, c, accumulate=accumulate)
+    e0, e1 = kernels.Event(), kernels.Event()
+    e0.record()
+    kernels.gemm_f32(a, b, c, accumulate=accumulate)
+    self.gemm_events.append((e0, e1.record(), a.shape[0], b.shape[1], a.shape[1]))      # (start, stop, M, N, K)
+    return c
+
   def gemm_into(self, a, b, out, accumulate=False):
     """out (+)= a . b for 2-D fp32 / fp64 tensors that may be strided views (inner stride 1): the building block
     of the pipelined joins (dot.ksplit_plan), one sp_gemm launch, nothing allocated."""
-    self.launches += 1
     self.gemms += 1
-    if self.gemm_events is not None:
-      e0, e1 = kernels.Event(), kernels.Event()
-      e0.record()
-      kernels.gemm_f32(a, b, out, accumulate=accumulate)
-      e1.record()
-      self.gemm_events.append((e0, e1, a.shape[0], b.shape[1], a.shape[1]))
-    else:
-      kernels.gemm_f32(a, b, out, accumulate=accumulate)
-    return out
+    return self._gemm(a, b, out, accumulate)
 
   def dot_chunked(self, a, rhs):
     """a . B with B arriving as column chunks (distarray.ChunkedWhole): one GEMM per chunk into the
@@ -977,22 +996,12 @@ class HipBackend(object):
         c0, c1, t = rhs.ready(i)
         self.paste(whole, (slice(0, rhs.shape[0]), slice(c0, c1)), t)
       return self.dot(a, whole)
-    M, K = a.shape
-    N = rhs.shape[1]
     if a.stride(1) != 1:
       a = self.copy(a)
-    c = self.empty((M, N), rhs.dtype)
+    c = self.empty((a.shape[0], rhs.shape[1]), rhs.dtype)
     for i in range(len(rhs.chunks)):
       c0, c1, t = rhs.ready(i)
-      self.launches += 1
-      if self.gemm_events is not None:
-        e0, e1 = kernels.Event(), kernels.Event()
-        e0.record()
-        kernels.gemm_f32(a, t, c[:, c0:c1], accumulate=False)
-        e1.record()
-        self.gemm_events.append((e0, e1, M, c1 - c0, K))
-      else:
-        kernels.gemm_f32(a, t, c[:, c0:c1], accumulate=False)
+      self._gemm(a, t, c[:, c0:c1])
     return c
 
   # -- k-means tile bodies (examples/sklearn/cluster/k_means_.py) ---------------------
@@ -1012,7 +1021,7 @@ class HipBackend(object):
     return t
 
   def _labels_i64(self, labels, n):
-    origin, _ = self._known_labels(labels)
+    origin = self._fit.known(labels)[0] if self._fit is not None else None
     if origin is not None and origin.numel() == n:
       return self.contiguous(origin).reshape(n)
     labels = self.astype(labels, np.int64) if self.dtype_of(labels) != np.int64 else labels
@@ -1023,30 +1032,28 @@ class HipBackend(object):
     points, centers = self._rows(self._as_device(points)), self._rows(self._as_device(centers))
     out = self.empty((points.shape[0],), np.int64)
     self.launches += 1
-    prepared = None
-    if self._fixed_points is not None and self.dtype_of(points) == np.float32 and points.shape[0] >= 1024:
-      # inside a fit (fixed_points): the points' bf16 images are made on their first use and kept to its end
-      key = (points.data_ptr(), tuple(points.shape), tuple(points.strides))
-      prepared = self._fixed_points.get(key)
-      if prepared is None:
-        if len(self._fixed_points) >= 64:      # (points that are re-made every iteration: keep nothing of them)
-          self._fixed_points.clear()
-        prepared = self._fixed_points[key] = (kernels.prepare_points(points), points)     # (the tile stays alive)
-      prepared = prepared[0]
-    out = kernels.nearest_center(points, centers, out, tier, prepared)
-    if self._fit_labels is not None and centers.shape[0] <= (1 << 24):
-      self._note_labels(out)           # (labels below 2^24: their float32 image is exact)
+    fit = self._fit
+    out = kernels.nearest_center(points, centers, out, tier, fit.prepared_for(points) if fit is not None else None)
+    if fit is not None and centers.shape[0] <= (1 << 24):
+      fit.note(out)           # (labels below 2^24: their float32 image is exact)
     return out
 
+  @contextlib.contextmanager
   def fixed_points(self):
     """with be.fixed_points(): -- the caller promises that the point tiles it passes to nearest_center are not
     written inside the block (the iterations of one k-means fit): what the kernels derive from the points alone is
-    then derived once per tile.  Nothing outlives the block."""
-    return _FixedPoints(self)
+    then derived once per tile (_Fit).  Nothing outlives the block; a block inside another adds nothing."""
+    outer = self._fit
+    if outer is None:
+      self._fit = _Fit()
+    try:
+      yield
+    finally:
+      self._fit = outer
 
   def bincount(self, labels, k):
     """np.bincount(labels.astype(int), minlength=k) -> int64 (k,)  (k_means_.py:69-72)."""
-    counts = self._take_counts(labels) if self._fit_labels is not None else None
+    counts = self._fit.take_counts(labels) if self._fit is not None else None
     if counts is not None and counts.numel() == int(k):
       return counts                    # counted by this fit's segment_sum of the same labels (sp_segment_sum_counts)
     labels = self._labels_i64(labels, int(np.prod(labels.shape)))
@@ -1060,15 +1067,15 @@ class HipBackend(object):
     labels = self._labels_i64(labels, points.shape[0])
     out = self.empty((int(k), points.shape[1]), self.dtype_of(points))
     self.launches += 1
-    if self._fit_labels is None:
+    if self._fit is None:
       return kernels.segment_sum(points, labels, int(k), out)
     # inside a fit the counts of the same labels are wanted too (kmeans_count_mapper): the counting sort has them
     counts = self.empty((int(k),), np.int64)
     kernels.segment_sum(points, labels, int(k), out, counts)
     if isinstance(given, D.DevArray):
-      self._note_labels(given, counts=counts)
+      self._fit.note(given, counts=counts)
     if labels is not given:
-      self._note_labels(labels, counts=counts)
+      self._fit.note(labels, counts=counts)
     return out
 
   def concat(self, a, b, axis=0):
@@ -1272,8 +1279,6 @@ class HipBackend(object):
     """A local map tree with sparse operands, node by node (the reference hands the scipy matrices to the
     NumPy function, local.py:115-127): sparse (+|-) sparse and scalings stay sparse; a ufunc over one sparse
     and one dense operand sees the sparse one densified (local.py:120-126); dense sub-trees are fused maps."""
-    from .expr import builtins as B
-
     def ev(node):
       if isinstance(node, LocalInput):
         return ex.to_tuple() if node.idx == 'extent' else inputs[node.idx]
@@ -1331,8 +1336,7 @@ class HipBackend(object):
 
   def liveness_probe(self, timeout_s=2.0):
     """One round trip through the device on a stream of its own (heartbeat.py): False if it does not come back."""
-    import time
-    if getattr(self, '_probe_stream', None) is None:
+    if self._probe_stream is None:
       self._probe_stream = D.Stream()
     ev = D.Event().record(self._probe_stream)
     deadline = time.time() + timeout_s

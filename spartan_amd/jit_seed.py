@@ -18,27 +18,20 @@ import os
 import numpy as np
 
 from . import _hip, devarray, kernels, sparse
-from .backend_hip import HipBackend
+from .backend_hip import HipBackend, _Lowered
+
+
+class _NothingLowered(_Lowered):
+  def key(self, op, inputs, ex, extra):
+    return None          # every program is lowered (and its specialisation requested) afresh
 
 
 class _SeedBackend(HipBackend):
   name = 'hip'
+  _lowered_type = _NothingLowered
 
-  def __init__(self):   # no device check: nothing is launched successfully in seed mode
-    import collections
-    self.device = 'seed'
-    self._np_cache = collections.OrderedDict()
-    self.launches = self.gemms = self.host_round_trips = 0
-    self._warned_host = set()
-    self.gemm_events = None
-    self._rng_seed, self._rng_offset = 1, 0
-    self._lowered = collections.OrderedDict()
-    self.lowering_hits = 0
-    self._side_copies, self._pinned_free = None, {}
-    self._fixed_points = None
-
-  def _lowering_key(self, op, inputs, ex, extra):
-    return None          # every program is lowered (and its specialisation requested) afresh
+  def __init__(self):   # no device check, no preload: nothing is launched successfully in seed mode
+    self._init_state(device='seed', rng_seed=1)
 
 
 @contextlib.contextmanager

@@ -37,6 +37,18 @@ def test_seeding_without_a_gpu_writes_the_code_objects(tmp_path):
     assert files == sorted(f for f in os.listdir(tree) if f.endswith('.spco'))
 
 
+def test_the_seed_backend_has_every_attribute_of_a_hip_backend():
+  """jit_seed's backend skips HipBackend.__init__ (no device): whatever state the methods it inherits read must be there
+  all the same.  (A HipBackend cannot be constructed without a GPU, so its state is set up on a bare instance.)"""
+  from spartan_amd.backend_hip import HipBackend
+  from spartan_amd.jit_seed import _SeedBackend
+  hip = HipBackend.__new__(HipBackend)
+  hip._init_state()
+  device_only = set()       # (names of attributes that only make sense with a device: none today)
+  missing = set(vars(hip)) - device_only - set(vars(_SeedBackend()))
+  assert not missing, sorted(missing)
+
+
 @pytest.mark.gpu
 def test_seeding_on_a_gpu_box(tmp_path):
   files = _seed_into(tmp_path)

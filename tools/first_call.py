@@ -27,10 +27,10 @@ orig_run = be._run_map
 def run_map(*a, **k):
   t0 = time.perf_counter(); r = orig_run(*a, **k); marks.append(('_run_map', (time.perf_counter() - t0) * 1e6)); return r
 be._run_map = run_map
-orig_key = be._lowering_key
+orig_key = be._lowered.key
 def lkey(*a, **k):
   t0 = time.perf_counter(); r = orig_key(*a, **k); marks.append(('key', (time.perf_counter() - t0) * 1e6)); return r
-be._lowering_key = lkey
+be._lowered.key = lkey
 pending = [(((Xv * Xv + Xv) * 0.5 - Xv) / (Xv + 2.0)).optimized() for _ in range(3)]
 for i, e in enumerate(pending):
   D.synchronize()
