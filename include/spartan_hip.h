@@ -325,6 +325,23 @@ size_t sp_rowdot_colsum_workspace_bytes(int64_t n, int64_t d);          /* 0: sh
 int sp_rowdot_colsum_f32(const float* d_x, int64_t ldx, int64_t n, int64_t d, const float* d_w, const float* d_y,
                          int64_t ldy, float* d_out, int32_t accumulate, void* d_ws, size_t ws_bytes, void* stream);
 
+/* sp_rowdot_link_colsum_f32: the same pass with a LINK between the row dot and the residual,
+ *   out[c] (+)= sum_i X[i][c] * (link(X[i,:] . w) - y[i])      (y == NULL: no subtraction)
+ * for the gradients of the reference's SGD family (spartan/examples/sgd.py:34-39).  link:
+ *   SP_LINK_IDENTITY  (0): t                                  -- sp_rowdot_colsum_f32, bit for bit
+ *   SP_LINK_EXP_RATIO (1): e = expf(t); e / (e + 1.f)         -- logistic_regression.py:15-16 as spelled there
+ *   SP_LINK_SIGMOID   (2): 1.f / (1.f + expf(-t))
+ * each computed as written in float32 (the map kernels' expf, IEEE division, nothing contracted): where expf(t)
+ * overflows, EXP_RATIO gives NaN (inf / inf) and SIGMOID 0 or 1, as NumPy's float32 does for the two-launch form.
+ * Contract, workspace (sp_rowdot_colsum_workspace_bytes), alignment, determinism and `accumulate` are
+ * sp_rowdot_colsum_f32's; any other link is an error. */
+#define SP_LINK_IDENTITY 0
+#define SP_LINK_EXP_RATIO 1
+#define SP_LINK_SIGMOID 2
+int sp_rowdot_link_colsum_f32(const float* d_x, int64_t ldx, int64_t n, int64_t d, const float* d_w, const float* d_y,
+                              int64_t ldy, int32_t link, float* d_out, int32_t accumulate, void* d_ws, size_t ws_bytes,
+                              void* stream);
+
 /* k-means tile kernels: the bodies of the reference's k-means mappers
  * (spartan/examples/sklearn/cluster/k_means_.py), BASELINE configs[3].
  *

@@ -927,6 +927,31 @@ class HipBackend(object):
     r = t if y is None else t - y.reshape(t.shape)
     return (x * r).sum(0)
 
+  def rowdot_link_colsum(self, x, w, y, link):
+    """(d,) partial of `sum(x * (link(dot(x, w)) - y), axis=0)` for one row tile, link one of _hip.SP_LINK_* (the
+    logistic gradients, expr/rowdot.py): one pass over x when the layout allows (sp_rowdot_link_colsum_f32), else
+    the launches the rewrite replaced -- the dot, the link element-wise on its (n, 1) result, the map -> column sum."""
+    if link not in (_hip.SP_LINK_IDENTITY, _hip.SP_LINK_EXP_RATIO, _hip.SP_LINK_SIGMOID):
+      raise ValueError('rowdot_link_colsum: unknown link %r' % (link,))
+    d = int(x.shape[1])
+    wd = self.cached_numpy(w, (slice(0, d),))
+    wd = wd.reshape(d)
+    yd = None
+    if y is not None:
+      yd = y.reshape(y.shape[0]) if y.dim() == 2 and y.shape[1] == 1 else y
+    out = self.empty((d,), np.float32)
+    self.launches += 1
+    if wd.is_contiguous() and (yd is None or yd.dim() == 1) and kernels.rowdot_link_colsum(x, wd, yd, out, link):
+      return out
+    t = self.dot(x, wd.reshape(d, 1))
+    if link == _hip.SP_LINK_EXP_RATIO:
+      e = np.exp(t)
+      t = e / (e + np.float32(1))
+    elif link == _hip.SP_LINK_SIGMOID:
+      t = np.float32(1) / (np.float32(1) + np.exp(-t))
+    r = t if y is None else t - y.reshape(t.shape)
+    return (x * r).sum(0)
+
   def dot(self, a, b):
     """ndarray.dot for backend tensors: MFMA GEMM for fp32 matrix.matrix, fused
     multiply-reduce launches for everything else."""

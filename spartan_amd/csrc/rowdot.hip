@@ -16,6 +16,14 @@
 // sums and column sums have their own trees), so results agree to rounding, not bit for bit; the expression
 // rewrite that selects this kernel (spartan_amd/expr/optimize.py: RowDotColSumFusion) is applied on the HIP
 // backend only and can be turned off (FLAGS['opt_rowdot_fusion']).
+//
+// The same pass serves the other gradient of the reference's SGD family, logistic regression
+// (spartan/examples/logistic_regression.py:15-17 through sgd.py:34-39): only the per-ROW residual differs,
+//     g = exp(dot(x, w)) ;  yp = g / (g + 1) ;  sum(x * (yp - y), axis=0)
+// so the residual step is a compile-time LINK (sp_rowdot_link_colsum_f32): identity (above), exp(t) / (exp(t) + 1) --
+// the reference's spelling -- and 1 / (1 + exp(-t)).  Each is computed exactly as spelled, with the expf of the map
+// kernels (sp_interp.hpp: exp_) and IEEE division, so overflow is NumPy float32's of the two-launch form: inf / inf
+// = NaN for the first spelling, 0 or 1 for the second.  One exp and one divide per row, all lanes alike.
 #include "sp_common.hpp"
 
 namespace {
@@ -26,9 +34,20 @@ constexpr int RD_WAVES = SP_CUS * 8;          // 192 VGPRs: two waves per SIMD, 
 
 typedef float rd_f4 __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(256, 2) void sp_rowdot_colsum_kernel(const float* __restrict__ X, int64_t ldx, int64_t n, int d,
-                                                                  const float* __restrict__ w, const float* __restrict__ y,
-                                                                  int64_t ldy, float* __restrict__ part) {
+// r = link(t) - y[i]; t is the butterfly's result, the same in every lane
+template <int LINK>
+__device__ __forceinline__ float rd_link(float t) {
+  if (LINK == SP_LINK_EXP_RATIO) {
+    const float e = expf(t);
+    return e / (e + 1.f);
+  }
+  if (LINK == SP_LINK_SIGMOID) return 1.f / (1.f + expf(-t));
+  return t;
+}
+
+template <int LINK>
+__device__ __forceinline__ void rd_rows(const float* __restrict__ X, int64_t ldx, int64_t n, int d, const float* __restrict__ w,
+                                        const float* __restrict__ y, int64_t ldy, float* __restrict__ part) {
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int nj = d >> 8;                       // whole 256-column pieces; the rest (a multiple of 4 columns) is piece nj
@@ -57,7 +76,8 @@ __global__ __launch_bounds__(256, 2) void sp_rowdot_colsum_kernel(const float* _
       for (int e = 0; e < 4; ++e) t += x[j][e] * wv[j][e];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-    const float r = y ? t - y[i * ldy] : t;
+    const float v = rd_link<LINK>(t);
+    const float r = y ? v - y[i * ldy] : v;
 #pragma unroll
     for (int j = 0; j < RD_J; ++j)
 #pragma unroll
@@ -86,6 +106,18 @@ __global__ __launch_bounds__(256, 2) void sp_rowdot_colsum_kernel(const float* _
       }
   }
 }
+
+// One kernel per link, each under a name of its own (traces and benchmarks name the identity kernel).
+#define RD_KERNEL(name, link)                                                                                          \
+  __global__ __launch_bounds__(256, 2) void name(const float* __restrict__ X, int64_t ldx, int64_t n, int d,            \
+                                                 const float* __restrict__ w, const float* __restrict__ y, int64_t ldy, \
+                                                 float* __restrict__ part) {                                            \
+    rd_rows<link>(X, ldx, n, d, w, y, ldy, part);                                                                       \
+  }
+RD_KERNEL(sp_rowdot_colsum_kernel, SP_LINK_IDENTITY)
+RD_KERNEL(sp_rowdot_exp_ratio_colsum_kernel, SP_LINK_EXP_RATIO)
+RD_KERNEL(sp_rowdot_sigmoid_colsum_kernel, SP_LINK_SIGMOID)
+#undef RD_KERNEL
 
 // out[c] (+)= part[0][c] + part[1][c] + ... in wave order.  Workgroup: 64 columns x 16 groups of waves.
 __global__ __launch_bounds__(1024) void sp_rowdot_finish_kernel(const float* __restrict__ part, int nwaves, int d,
@@ -129,9 +161,10 @@ extern "C" size_t sp_rowdot_colsum_workspace_bytes(int64_t n, int64_t d) {
   return (size_t)rd_waves(n) * (size_t)d * 4 + 256;
 }
 
-extern "C" int sp_rowdot_colsum_f32(const float* d_x, int64_t ldx, int64_t n, int64_t d, const float* d_w, const float* d_y,
-                                    int64_t ldy, float* d_out, int32_t accumulate, void* d_ws, size_t ws_bytes,
-                                    void* stream) {
+extern "C" int sp_rowdot_link_colsum_f32(const float* d_x, int64_t ldx, int64_t n, int64_t d, const float* d_w, const float* d_y,
+                                         int64_t ldy, int32_t link, float* d_out, int32_t accumulate, void* d_ws,
+                                         size_t ws_bytes, void* stream) {
+  if (link != SP_LINK_IDENTITY && link != SP_LINK_EXP_RATIO && link != SP_LINK_SIGMOID) SP_FAIL("sp_rowdot_link_colsum_f32: unknown link %d", (int)link);
   if (n < 0 || d < 4 || d > RD_MAX_D || d % 4) SP_FAIL("sp_rowdot_colsum_f32: needs 4 <= d <= %d, d %% 4 == 0 (got %lld)", RD_MAX_D, (long long)d);
   if (!d_out || !d_w || (n && !d_x)) SP_FAIL("sp_rowdot_colsum_f32: NULL pointer");
   if (ldx < d || ldx % 4 || (((uintptr_t)d_x | (uintptr_t)d_w | (uintptr_t)d_out) & 15)) SP_FAIL("sp_rowdot_colsum_f32: X rows, w and out must be 16-byte aligned");
@@ -144,10 +177,20 @@ extern "C" int sp_rowdot_colsum_f32(const float* d_x, int64_t ldx, int64_t n, in
   if (!d_ws || ws_bytes < need) SP_FAIL("sp_rowdot_colsum_f32: workspace too small (%zu < %zu)", ws_bytes, need);
   float* part = (float*)(((uintptr_t)d_ws + 255) & ~(uintptr_t)255);
   const int waves = rd_waves(n);
-  hipLaunchKernelGGL(sp_rowdot_colsum_kernel, dim3(waves / 4), dim3(256), 0, st, d_x, ldx, n, (int)d, d_w, d_y, ldy < 1 ? 1 : ldy, part);
+  auto kernel = link == SP_LINK_EXP_RATIO ? sp_rowdot_exp_ratio_colsum_kernel
+                : link == SP_LINK_SIGMOID ? sp_rowdot_sigmoid_colsum_kernel
+                                          : sp_rowdot_colsum_kernel;
+  hipLaunchKernelGGL(kernel, dim3(waves / 4), dim3(256), 0, st, d_x, ldx, n, (int)d, d_w, d_y, ldy < 1 ? 1 : ldy, part);
   SP_CHECK_LAUNCH();
   hipLaunchKernelGGL(sp_rowdot_finish_kernel, dim3((unsigned)((d + 63) / 64)), dim3(1024), 0, st, (const float*)part, waves / 4,
                      (int)d, d_out, (int)accumulate);
   SP_CHECK_LAUNCH();
   return 0;
+}
+
+// the identity link under the name it has always had: same kernel, same launches, same bits
+extern "C" int sp_rowdot_colsum_f32(const float* d_x, int64_t ldx, int64_t n, int64_t d, const float* d_w, const float* d_y,
+                                    int64_t ldy, float* d_out, int32_t accumulate, void* d_ws, size_t ws_bytes,
+                                    void* stream) {
+  return sp_rowdot_link_colsum_f32(d_x, ldx, n, d, d_w, d_y, ldy, SP_LINK_IDENTITY, d_out, accumulate, d_ws, ws_bytes, stream);
 }

@@ -40,8 +40,9 @@ FLAGS = {
     'opt_rotate_slice': False,        # off by default in the reference as well (optimize.py:1095)
     'opt_map_fusion': True,
     'opt_reduce_fusion': True,
-    # not a rewrite of the reference's: sum(x * (dot(x, w) - y), axis=0) in one pass over x (expr/rowdot.py), applied
-    # only where the backend has the kernel
+    # not a rewrite of the reference's: sum(x * (dot(x, w) - y), axis=0) -- and the logistic gradients, the same sum
+    # with exp(t) / (exp(t) + 1) or 1 / (1 + exp(-t)) of the dot -- in one pass over x (expr/rowdot.py), applied only
+    # where the backend has the kernel
     'opt_rowdot_fusion': True,
     # not a rewrite: DAGs with the structure of one seen before take its recorded result (expr/plan.py)
     'opt_plan_cache': True,
@@ -172,7 +173,13 @@ class ReduceMapFusion(Pass):
 class RowDotColSumFusion(Pass):
   """reduce(sum, axis=0, x * (dot(x, w) - y))  ->  one pass over the rows of x (expr/rowdot.py).  Runs after
   ReduceMapFusion, on the shape that pass leaves: a column sum whose fused operator is multiply(a, subtract(b, c))
-  (or multiply(a, b)) over the inputs x, dot(x, w) = the map2 join with a driver-side vector, and y."""
+  (or multiply(a, b)) over the inputs x, dot(x, w) = the map2 join with a driver-side vector, and y.
+
+  With t = that dot, b may also be a LINK of it, exactly one of
+      divide(exp(t), add(exp(t), 1))              the reference's logistic_regression.py:15-16
+      divide(1, add(1, exp(negative(t))))
+  (both exp over the SAME dot, the add in either order, 1 a driver-side Python or float32 scalar) -- taken only when
+  the backend has `rowdot_link_colsum`; a backend with `rowdot_colsum` alone keeps the least-squares rewrite."""
   name = 'rowdot_fusion'
   rules = {'ReduceExpr': 'fuse'}
 
@@ -181,8 +188,8 @@ class RowDotColSumFusion(Pass):
     if found is None:
       return node
     from .rowdot import RowDotColSumExpr
-    x, w, y = found
-    return RowDotColSumExpr(expr_id=node.expr_id, x=x, y=y, w=w, tile_hint=node.tile_hint)
+    x, w, y, link = found
+    return RowDotColSumExpr(expr_id=node.expr_id, x=x, y=y, w=w, tile_hint=node.tile_hint, link=link)
 
   @staticmethod
   def match(node):
@@ -191,10 +198,12 @@ class RowDotColSumFusion(Pass):
     from . import builtins
     from .local import LocalMapExpr
     from .map import Map2Expr
+    from .rowdot import LINK_EXP_RATIO, LINK_IDENTITY, LINK_SIGMOID
     dot_mod = sys.modules.get(__package__ + '.dot') or importlib.import_module(__package__ + '.dot')   # (the package
     # attribute `dot` is the builder, not the module)
     if not context.initialized() or getattr(context.get().backend, 'rowdot_colsum', None) is None:
       return None
+    with_links = getattr(context.get().backend, 'rowdot_link_colsum', None) is not None
     if node.axis != 0 or node.accumulate_fn is not np.add or node.op.fn is not builtins._sum_local:
       return None
     data = [d for d in node.op.deps if not isinstance(d, LocalInput)]
@@ -232,22 +241,50 @@ class RowDotColSumFusion(Pass):
         return None
       return e
 
+    def is_one(d):
+      """The constant 1 as a driver-side scalar that leaves a float32 operand float32."""
+      e = leaf(d)
+      v = e.val if isinstance(e, AsArray) else None
+      return type(v) in (int, float, np.float32) and v == 1
+
+    def call(d, fn, n):
+      return isinstance(d, LocalMapExpr) and d.fn is fn and not d.kw and len(d.deps) == n
+
+    def linked(b):
+      """(link, the dot's node) for b = L(t) over ONE input variable t, or the identity for an input itself."""
+      if isinstance(b, LocalInput):
+        return LINK_IDENTITY, leaf(b)
+      if not with_links or not call(b, np.divide, 2) or not call(b.deps[1], np.add, 2):
+        return None
+      num, den = b.deps[0], b.deps[1].deps
+      for one, e in (den, den[::-1]):
+        if not is_one(one) or not call(e, np.exp, 1):
+          continue
+        arg = e.deps[0]
+        if call(num, np.exp, 1) and isinstance(num.deps[0], LocalInput) and isinstance(arg, LocalInput) \
+            and num.deps[0].idx == arg.idx:                                        # exp(t) / (exp(t) + 1)
+          return LINK_EXP_RATIO, leaf(arg)
+        if is_one(num) and call(arg, np.negative, 1) and isinstance(arg.deps[0], LocalInput):   # 1 / (1 + exp(-t))
+          return LINK_SIGMOID, leaf(arg.deps[0])
+      return None
+
     for a, b in (data[0].deps, data[0].deps[::-1]):
       x = leaf(a) and as_x(leaf(a))
       if not x:
         continue
-      if isinstance(b, LocalInput):                      # x * dot(x, w)
-        w = as_dot(leaf(b), x)
-        if w is not None and len(w.shape) == 2:
-          return x, w, None
-      elif isinstance(b, LocalMapExpr) and b.fn is np.subtract and len(b.deps) == 2:   # x * (dot(x, w) - y)
-        t, yv = leaf(b.deps[0]), leaf(b.deps[1])
-        if t is None or yv is None:
+      yv = None
+      if call(b, np.subtract, 2):                          # x * (L(dot(x, w)) - y)
+        b, yv = b.deps[0], leaf(b.deps[1])
+        if yv is None:
           continue
-        w = as_dot(t, x)
-        y = as_y(yv, x)
-        if w is not None and len(w.shape) == 2 and y is not None:
-          return x, w, y
+      found = linked(b)
+      if found is None or found[1] is None:
+        continue
+      link, t = found
+      w = as_dot(t, x)
+      y = as_y(yv, x) if yv is not None else None
+      if w is not None and len(w.shape) == 2 and (yv is None or y is not None):
+        return x, w, y, link
     return None
 
 

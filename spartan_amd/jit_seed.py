@@ -79,6 +79,23 @@ def default_programs(sp):
   return progs
 
 
+def column_programs(sp):
+  """The launches the one-pass gradient rewrite (expr/rowdot.py) replaces, which a layout its kernel refuses -- or
+  FLAGS['opt_rowdot_fusion'] = False -- runs instead: over a tile `x` and (rows, 1) columns `t` (the dot's result) and
+  `y`, the link as a map of its own and the fused map -> column sum, for the least-squares residual and the two
+  spellings of the logistic one (examples/lreg.py, examples/logreg.py)."""
+  def progs(x, t, y):
+    ratio = lambda: sp.exp(t) / (sp.exp(t) + 1)              # noqa: E731
+    sigmoid = lambda: 1 / (1 + sp.exp(-t))                   # noqa: E731
+    return [
+        ratio(), sigmoid(), ratio() - y, sigmoid() - y,
+        sp.sum(x * t, axis=0), sp.sum(x * (t - y), axis=0),
+        sp.sum(x * ratio(), axis=0), sp.sum(x * (ratio() - y), axis=0),
+        sp.sum(x * sigmoid(), axis=0), sp.sum(x * (sigmoid() - y), axis=0),
+    ]
+  return progs
+
+
 def seed(directory=None, verbose=False):
   """Compile and store the specialisations of default_programs for fp32 and fp64 tiles, small enough to stay in the
   L2 and larger (the two differ in their load / store hints).  Returns the number of code objects written."""
@@ -104,6 +121,16 @@ def seed(directory=None, verbose=False):
             except Exception as err:   # noqa: BLE001  (a program this build cannot lower is simply not seeded)
               if verbose:
                 print('jit_seed: skipped %s: %s' % (type(err).__name__, err))
+      cols = column_programs(sp)
+      for shape in shapes:                                   # (the gradient kernels, hence their stand-ins, are fp32)
+        x = sp.from_tile_fn(shape, np.float32, lambda ex: devarray.empty(ex.shape, np.float32))
+        mk = lambda: sp.from_tile_fn((shape[0], 1), np.float32, lambda ex: devarray.empty(ex.shape, np.float32))   # noqa: E731
+        for e in cols(x, mk(), mk()):
+          try:
+            e.optimized().force()
+          except Exception as err:   # noqa: BLE001
+            if verbose:
+              print('jit_seed: skipped %s: %s' % (type(err).__name__, err))
     finally:
       _context.set(prev)
       _base.eval_cache.clear()
