@@ -305,6 +305,11 @@ int sp_gemm_f64(const double* d_A, int64_t lda, const double* d_B, int64_t ldb, 
  * partial products are added in slice order (deterministic, no atomics).  Without scratch, or when no
  * split pays, it is exactly sp_gemm_f32 / sp_gemm_f64. */
 size_t sp_gemm_workspace_bytes(int32_t dtype, int64_t M, int64_t N, int64_t K);
+/* The fp32 split tier (csrc/gemm_split.hpp: three bf16 pieces per operand, six exact products per k on the bf16
+ * matrix pipe) needs room for its operand images: sp_gemm_ws takes that tier when d_ws holds at least
+ * sp_gemm_split_workspace_bytes(...) bytes (0: the shape stays on the kernels above; a caller hands sp_gemm_ws the
+ * larger of the two sizes).  SP_GEMM_SPLIT=0 in the environment, read once, makes it 0 everywhere. */
+size_t sp_gemm_split_workspace_bytes(int32_t dtype, int64_t M, int64_t N, int64_t K);
 int sp_gemm_ws(int32_t dtype, const void* d_A, int64_t lda, const void* d_B, int64_t ldb, void* d_C,
                int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t accumulate, void* d_ws,
                size_t ws_bytes, void* stream);

@@ -1,5 +1,12 @@
-// fp32 GEMM on the CDNA4 f32-input MFMA (v_mfma_f32_32x32x2_f32): exact fp32
-// (bitwise an fmaf chain in k order), 157.3 TFLOP/s peak on MI355X.
+// fp32 GEMM, two tiers.  The fp32 tier runs on the CDNA4 f32-input MFMA (v_mfma_f32_32x32x2_f32): exact fp32
+// (bitwise an fmaf chain in k order), 157.3 TFLOP/s peak on MI355X.  The split tier (gemm_split.hpp; sp_gemm_ws takes it
+// for large aligned problems when it is handed a workspace, SP_GEMM_SPLIT=0 turns it off) cuts every operand into
+// three bf16 pieces and takes six exact products per k on the bf16 MFMA, accumulated in fp32: with S = sum_k |a_k b_k|
+// and u = 2^-24 it differs from the exact product by at most 2.004 u S (three products left out) plus the fp32
+// accumulation of 6 K exact addends -- bounded by 6.05 K u S for any order of adding them, measured on the instruction
+// at 0.94 K u (S + max|c|) -- where the fmaf chain's bound is K u S; a product that is exact in fp32 (integer-valued
+// operands) is exact in both tiers, and operands outside the tier's exponent window (2^-40 <= |v| < 2^40, or zero) get
+// the fp32 tier's bits.
 //
 // Replaces `tiles[0].dot(tiles[1])` of the reference's dot mappers
 // (spartan/expr/dot.py:195-217 dot_map2_mapper, :222-238 dot_outer_mapper,
@@ -306,8 +313,10 @@ struct GldsCfg {
 // between the halves, 146.6.  k-tiles of 32 in the register-staged kernel (half the barriers per contraction) were
 // slower too (profiles/r01_notes.md).
 // WGS: workgroups per CU the register allocation aims for.
-template <typename Cfg, int BM, int BN, int WM, int WN, int WGS>
-__global__ __launch_bounds__(Cfg::THREADS, WGS) void sp_gemm_glds_kernel(
+// (the body is a __device__ function with two entry points: sp_gemm_glds_kernel below, and the split tier's
+// fallback behind its device flag, sp_gemm_f32_gated_kernel in gemm_split.hpp)
+template <typename Cfg, int BM, int BN, int WM, int WN>
+__device__ __forceinline__ void sp_gemm_glds_body(
     const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, float* __restrict__ C,
     int64_t ldc, int M, int N, int K, int accumulate, int tiles_m, int tiles_n) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -450,6 +459,13 @@ __global__ __launch_bounds__(Cfg::THREADS, WGS) void sp_gemm_glds_kernel(
       }
     }
   }
+}
+
+template <typename Cfg, int BM, int BN, int WM, int WN, int WGS>
+__global__ __launch_bounds__(Cfg::THREADS, WGS) void sp_gemm_glds_kernel(
+    const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, float* __restrict__ C,
+    int64_t ldc, int M, int N, int K, int accumulate, int tiles_m, int tiles_n) {
+  sp_gemm_glds_body<Cfg, BM, BN, WM, WN>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, tiles_m, tiles_n);
 }
 
 template <int BM, int BN, int WM, int WN, int WGS>
@@ -909,6 +925,14 @@ static bool sp_sk_plan(int64_t M, int64_t N, int64_t K) {
   return sk_s < 0.97 * dp_s;
 }
 
+#include "gemm_split.hpp"
+
+// What the split tier (gemm_split.hpp) needs on top of sp_gemm_workspace_bytes: 0 where sp_gemm_ws would not take it.
+extern "C" size_t sp_gemm_split_workspace_bytes(int32_t dtype, int64_t M, int64_t N, int64_t K) {
+  if (M < 1 || N < 1 || dtype != SP_F32 || sp_split_plan(M, N, K, 16).splits > 1 || !sp_gemm_bf16_plan(M, N, K)) return 0;
+  return sp_gemm_bf16_ws_bytes(M, N, K);
+}
+
 extern "C" size_t sp_gemm_workspace_bytes(int32_t dtype, int64_t M, int64_t N, int64_t K) {
   if (M < 1 || N < 1 || (dtype != SP_F32 && dtype != SP_F64)) return 0;
   const SplitPlan pl = sp_split_plan(M, N, K, dtype == SP_F32 ? 16 : 8);
@@ -926,6 +950,16 @@ extern "C" int sp_gemm_ws(int32_t dtype, const void* d_A, int64_t lda, const voi
   if (dtype != SP_F32 && dtype != SP_F64) SP_FAIL("sp_gemm_ws: dtype must be f32 or f64");
   const SplitPlan pl = (M > 0 && N > 0) ? sp_split_plan(M, N, K, dtype == SP_F32 ? 16 : 8) : SplitPlan{1, 0};
   const size_t need = sp_gemm_workspace_bytes(dtype, M, N, K);
+  // the split tier (gemm_split.hpp): the direct-to-LDS preconditions of sp_gemm_f32's 256 x 128 kernel, which is its
+  // fallback, plus a C the epilogue can address the same way; anything else is the fp32 tier's
+  const bool bf16x3 = dtype == SP_F32 && pl.splits <= 1 && M > 0 && N > 0 && sp_gemm_bf16_plan(M, N, K);
+  if (bf16x3 && d_ws && ws_bytes >= sp_gemm_bf16_ws_bytes(M, N, K) && d_A && d_B && d_C && lda >= K && ldb >= N && ldc >= N && lda % 4 == 0 &&
+      ldb % 4 == 0 && ((((uintptr_t)d_A) | ((uintptr_t)d_B)) & 15) == 0 && (int64_t)256 * lda < (1LL << 30) &&
+      (int64_t)16 * ldb < (1LL << 30))
+    return sp_gemm_bf16_launch((const float*)d_A, lda, (const float*)d_B, ldb, (float*)d_C, ldc, M, N, K, accumulate,
+                               d_ws, (hipStream_t)stream);
+  if (bf16x3)   // (no workspace, or operands the tier does not take)
+    return sp_gemm_f32((const float*)d_A, lda, (const float*)d_B, ldb, (float*)d_C, ldc, M, N, K, accumulate, stream);
   if (pl.splits <= 1 && need && d_ws && ws_bytes >= need && dtype == SP_F32 && d_A && d_B && d_C && lda >= K &&
       ldb >= N && ldc >= N && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 &&
       ((((uintptr_t)d_A) | ((uintptr_t)d_B) | ((uintptr_t)d_C)) & 15) == 0 && (int64_t)256 * lda < (1LL << 30) &&

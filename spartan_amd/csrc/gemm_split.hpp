@@ -1,0 +1,391 @@
+// Split tier of sp_gemm_ws (fp32): the contraction on the bf16 matrix pipe, which on gfx950 runs at 16 x the rate of
+// the fp32 one (v_mfma_f32_32x32x16_bf16: 16 k per 32 cycles; v_mfma_f32_32x32x2_f32: 2 per 64).  Included by gemm.hip.
+//
+// THE CUT.  Every fp32 operand is cut into three bf16 numbers, v = hi + mid + lo with hi = bf16(v), mid = bf16(v - hi),
+// lo = bf16((v - hi) - mid), all conversions round-to-nearest-even.  bf16 keeps 8 significant bits, so for v in
+// [2^e, 2^(e+1)) the first remainder is a multiple of ulp(v) = 2^(e-23) no larger than 2^(e-8) <= 2^-8 |v| -- 16 bits and
+// a sign --, the second one no larger than 2^(e-16) <= 2^-16 |v| -- 8 bits and a sign: both subtractions are exact in fp32,
+// lo is exact and the cut loses nothing, 24 significand bits as 8 + 8 + 8 (tests/test_gemm_split_cut.py shows it on the
+// bit patterns).
+//
+// THE PRODUCTS.  a b = sum of the nine piece products; six are taken per 16 k, into one fp32 accumulator:
+//     ah bh, ah bm, am bh, am bm, ah bl, al bh
+// each EXACT in fp32 (8 x 8 significant bits).  The three left out are
+//     |am bl| + |al bm| + |al bl| <= (2^-8 2^-16 + 2^-16 2^-8 + 2^-32) |a b| <= 2.004 u |a b|,   u = 2^-24:
+// the size of the rounding of ONE fp32 product, and of either sign (summed over uniform data they cancel to
+// 0.004 u sum|a b|).  They vanish altogether when a b is itself exact in fp32 (a with p significant bits and b with q,
+// p + q <= 24: am bl != 0 needs p > 8 and q > 16, al bm != 0 p > 16 and q > 8), so integer-valued GEMMs whose fp32
+// result is exact stay bit-exact here.
+//
+// THE BOUND.  With S = sum_k |a_k b_k|, the result differs from the exact product by
+//   * the terms left out:                                        <= 2.004 u S
+//   * the accumulation of the 6 K exact products in fp32:        any order of adding n numbers with one rounding to
+//     nearest per addend errs by at most (n - 1) u sum|p| (1 + O(n u)); sum|p| <= (1 + 2^-8)^2 S, so <= 6.05 K u S.
+//     What the instruction does inside is not documented; measured (tools/mfma_bf16_probe.hip, see kmeans_split.hpp):
+//     at most 2.5 u (|c| + sum|p|) per MFMA of 16 products, i.e. 6 K / 16 MFMAs per element -> 0.94 K u (S + max|c|)
+//   * the epilogue's one rounding of C += (accumulate)           (as in the fp32 tier)
+// against the fp32 tier's k-ordered fmaf chain, K u S.  For uniform [-1, 1) data S ~ K / 4 and the errors add like a
+// random walk; measured ratios of the two tiers' max errors are in profiles/gemm_bf16_split_notes.md.
+//
+// THE WINDOW.  The above needs no piece to be a bf16 subnormal (the matrix pipe may flush them), no product to
+// underflow and no partial sum to overflow.  The cut passes check every element: it must be zero or satisfy
+//     2^-40 <= |v| < 2^40.
+//   * pieces: a nonzero piece of v in [2^e, 2^(e+1)) is a multiple of ulp(v) = 2^(e-23) >= 2^-63, far above bf16's
+//     smallest normal 2^-126 (bf16 has fp32's exponent range);
+//   * products: nonzero piece products are multiples of 2^-63 2^-63 = 2^-126, fp32's smallest normal, and so is any
+//     sum of them: neither a product nor a partial sum is ever a nonzero subnormal;
+//   * overflow: |pieces| <= 2^40 (1 + 2^-8), the six products of one k sum to < 1.02 2^80 in magnitude, and K < 2^31 of
+//     them to < 2^112 < 2^128.
+// An element outside the window -- or a NaN / Inf -- ORs a device flag.  The mainloop kernel returns at once when the
+// flag is set, and a gated launch of the fp32 kernel (sp_gemm_f32_gated_kernel: the body of sp_gemm_glds_kernel) that
+// follows it returns at once when it is clear: stream-ordered, no host wait, and such inputs get the fp32 tier's bits.
+//
+// IMAGES.  One pass per operand writes its three bf16 images k-tile-major, [K / 16][rows][16] (the layout
+// sp_split_rows_kernel in kmeans_split.hpp documents: the k-tile of the rows a workgroup brings per k-step is one
+// contiguous block), K padded to 16 with zeros.  A [M][K] is cut as it lies; B [K][N] must be k-contiguous per column,
+// so its pass transposes a 16 x 256 block through LDS.  Nothing is kept between calls: every call cuts its operands.
+// Shapes whose images would not fit under GS_IMAGE_CAP stay on the fp32 tier (cutting K into slabs that accumulate
+// into C is not built: 32768^3 would need seven).
+//
+// MAINLOOP (sp_gemm_glds_kernel_bf16x3).  256 x (64 WN) workgroup tile, 2 x WN waves of 128 x 64 each (the k-means
+// split kernel's geometry), k-tiles of 16 brought by global_load_lds_dwordx4 into two LDS stages, the pieces of a
+// request spread over the MFMAs of the k-step before; 18 ds_read_b128 fragment reads and 48 MFMAs per wave and k-step.
+// An LDS image is [row][2 chunks of 16 B]; chunk q of row r lives in slot q ^ ((r >> 4) & 1): a ds_read_b128 is served
+// in groups of 16 lanes -- rows {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of a fragment's 32 -- and the banks repeat
+// every 8 rows of 32 B, so inside a group the rows below 16 and the rows from 16 on that share their banks are sent
+// to different halves of them: conflict-free.  A lane's fragment is 8 consecutive k of one row for both operands.
+#pragma once
+
+typedef __bf16 gs_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 gs_bf16x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int GS_BK = 16;                         // k per k-tile
+constexpr int GS_RB = GS_BK * 2;                  // bytes of a row of a k-tile of one image
+constexpr int GS_WN = 4;                          // workgroup tile 256 x (64 GS_WN)
+constexpr unsigned GS_WIN_LO = (127u - 40u) << 23;   // bits of 2^-40
+constexpr unsigned GS_WIN_HI = (127u + 40u) << 23;   // bits of 2^40
+constexpr size_t GS_IMAGE_CAP = (size_t)2 << 30;  // bytes of operand images the tier may ask the workspace pool for
+constexpr size_t GS_WS_HEAD = 512;                // the flag, and room to align what follows
+
+template <int WN>
+struct GsCfg {
+  static constexpr int BM = 256, BN = 64 * WN, NW = 2 * WN, THREADS = 64 * NW;
+  static constexpr int A_BYTES = BM * GS_RB, B_BYTES = BN * GS_RB;      // one image of a k-tile
+  static constexpr int STAGE_BYTES = 3 * A_BYTES + 3 * B_BYTES;         // Ah | Am | Al | Bh | Bm | Bl
+  static constexpr int SMEM_BYTES = 2 * STAGE_BYTES;
+  static constexpr int APW = A_BYTES / 1024 / NW, BPW = B_BYTES / 1024 / NW;   // 1-KiB pieces per wave and image
+  static constexpr int NPIECES = 3 * APW + 3 * BPW;
+  static constexpr int SLOTS = SP_CUS * (WN == 4 ? 1 : 2);              // resident workgroups
+  static_assert(APW >= 1 && BPW >= 1 && APW * NW * 1024 == A_BYTES && BPW * NW * 1024 == B_BYTES, "tile / waves mismatch");
+  static_assert(NPIECES * 4 <= 48, "one piece after every fourth MFMA");
+};
+
+__device__ __forceinline__ bool gs_outside(float v) {
+  const unsigned b = __float_as_uint(v) & 0x7fffffffu;
+  return b != 0u && (b < GS_WIN_LO || b >= GS_WIN_HI);      // (NaN and Inf lie above GS_WIN_HI)
+}
+
+__device__ __forceinline__ void gs_cut(float v, __bf16& h, __bf16& m, __bf16& l) {
+  h = (__bf16)v;
+  const float r1 = v - (float)h;
+  m = (__bf16)r1;
+  l = (__bf16)(r1 - (float)m);
+}
+
+__device__ __forceinline__ void gs_raise(bool bad, unsigned* flag) {
+  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+
+// Images of A [M][K]: [KT][M][16] each, `img` apart.  A lane takes 4 consecutive k of one row;
+// 8 lanes a row's 32 k (two k-tiles), a wave 8 rows, a workgroup 32 rows x 256 k.
+__global__ __launch_bounds__(256) void sp_gemm_cut_rows_kernel(const float* __restrict__ A, int64_t lda, int M, int K,
+                                                               __bf16* __restrict__ Ah, int64_t img,
+                                                               unsigned* __restrict__ flag) {
+  const int q = threadIdx.x & 7, row = blockIdx.x * 32 + (threadIdx.x >> 3);
+  const int kpad = (K + GS_BK - 1) / GS_BK * GS_BK;
+  bool bad = false;
+  if (row < M) {
+    const float* __restrict__ a = A + (int64_t)row * lda;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int k = blockIdx.y * 256 + it * 32 + 4 * q;
+      if (k >= kpad) break;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (k + 4 <= K) {
+        v = *(const f32x4*)(a + k);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (k + e < K) v[e] = a[k + e];
+      }
+      gs_bf16x4 h, m, l;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        bad |= gs_outside(v[e]);
+        __bf16 hh, mm, ll;
+        gs_cut(v[e], hh, mm, ll);
+        h[e] = hh;
+        m[e] = mm;
+        l[e] = ll;
+      }
+      const int64_t at = ((int64_t)(k >> 4) * M + row) * GS_BK + (k & 15);
+      *(gs_bf16x4*)(Ah + at) = h;
+      *(gs_bf16x4*)(Ah + img + at) = m;
+      *(gs_bf16x4*)(Ah + 2 * img + at) = l;
+    }
+  }
+  gs_raise(bad, flag);
+}
+
+// Images of B [K][N]: [KT][N][16] each.  A workgroup takes one k-tile of 256 columns: lane = column,
+// 16 loads down k (a wave reads 256 B of a row per load), the three 32-byte image rows of its column through LDS, and
+// the 8 KiB of each image go out as they lie there, 16 B per lane.
+__global__ __launch_bounds__(256) void sp_gemm_cut_cols_kernel(const float* __restrict__ B, int64_t ldb, int N, int K,
+                                                               __bf16* __restrict__ Bh, int64_t img,
+                                                               unsigned* __restrict__ flag) {
+  __shared__ __attribute__((aligned(16))) __bf16 s[3][256 * GS_BK];
+  const int n0 = blockIdx.x * 256, col = n0 + threadIdx.x, k0 = blockIdx.y * GS_BK;
+  float v[GS_BK];
+#pragma unroll
+  for (int e = 0; e < GS_BK; ++e) v[e] = (col < N && k0 + e < K) ? B[(int64_t)(k0 + e) * ldb + col] : 0.f;
+  bool bad = false;
+  gs_bf16x8 h[2], m[2], l[2];
+#pragma unroll
+  for (int e = 0; e < GS_BK; ++e) {
+    bad |= gs_outside(v[e]);
+    __bf16 hh, mm, ll;
+    gs_cut(v[e], hh, mm, ll);
+    h[e >> 3][e & 7] = hh;
+    m[e >> 3][e & 7] = mm;
+    l[e >> 3][e & 7] = ll;
+  }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    *(gs_bf16x8*)(&s[0][threadIdx.x * GS_BK + 8 * c]) = h[c];
+    *(gs_bf16x8*)(&s[1][threadIdx.x * GS_BK + 8 * c]) = m[c];
+    *(gs_bf16x8*)(&s[2][threadIdx.x * GS_BK + 8 * c]) = l[c];
+  }
+  __syncthreads();
+  const int64_t base = ((int64_t)blockIdx.y * N + n0) * GS_BK;
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int at = (c * 256 + threadIdx.x) * 8;            // element of the 256 x 16 block; its row: at / 16
+      if (n0 + at / GS_BK < N) *(gs_bf16x8*)(Bh + p * img + base + at) = *(const gs_bf16x8*)(&s[p][at]);
+    }
+  gs_raise(bad, flag);
+}
+
+// The mainloop.  Ah / Bh: the hi images, mid and lo `a_img` / `b_img` BYTES behind; KT k-tiles.
+template <int WN>
+__global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf16x3(
+    const char* __restrict__ Ah, int64_t a_img, const char* __restrict__ Bh, int64_t b_img, float* __restrict__ C,
+    int64_t ldc, int M, int N, int KT, int accumulate, int tiles_m, int tiles_n, const unsigned* __restrict__ flag) {
+  using G = GsCfg<WN>;
+  constexpr int APW = G::APW, BPW = G::BPW, NPIECES = G::NPIECES;
+  extern __shared__ __attribute__((aligned(16))) char gs_smem[];
+  if (*flag != 0u) return;                                   // an operand left the window: the gated fp32 launch computes C
+  int tm, tn;
+  sp_gemm_tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n, tm, tn);
+  const int m0 = tm * G::BM, n0 = tn * G::BN;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wid / WN, wn = wid % WN;                    // wm: which 128 rows, wn: which 64 columns
+  const int l31 = lane & 31, lh = lane >> 5;
+
+  // ---- k-tile pieces: 1 KiB = one wave-wide 16-B load = 32 rows of one image; rows past the operand's end repeat
+  // its last row (their results are masked on store)
+  unsigned a_off[APW], b_off[BPW];
+#pragma unroll
+  for (int j = 0; j < APW; ++j) {
+    const int slot = (wid * APW + j) * 64 + lane;
+    int row = slot >> 1;
+    const int q = (slot & 1) ^ ((row >> 4) & 1);
+    if (m0 + row > M - 1) row = M - 1 - m0;
+    a_off[j] = (unsigned)(row * GS_RB + q * 16);
+  }
+#pragma unroll
+  for (int j = 0; j < BPW; ++j) {
+    const int slot = (wid * BPW + j) * 64 + lane;
+    int row = slot >> 1;
+    const int q = (slot & 1) ^ ((row >> 4) & 1);
+    if (n0 + row > N - 1) row = N - 1 - n0;
+    b_off[j] = (unsigned)(row * GS_RB + q * 16);
+  }
+  const char* __restrict__ Ablk = Ah + (int64_t)m0 * GS_RB;
+  const char* __restrict__ Bblk = Bh + (int64_t)n0 * GS_RB;
+  const int64_t a_slab = (int64_t)M * GS_RB, b_slab = (int64_t)N * GS_RB;     // bytes per k-tile of an image
+  const unsigned s_base = SP_LDS_ADDR(gs_smem);
+
+  // piece i of the request for k-tile kt_ into stage st_: image i / (APW or BPW) of A, then of B
+#define GS_PIECE(i)                                                                                    \
+  do {                                                                                                 \
+    if ((i) < 3 * APW) {                                                                               \
+      const int p_ = (i) / APW, j_ = (i) % APW;                                                        \
+      SP_GLDS_S(Ablk + p_ * a_img + ka_, a_off[j_], st_ + p_ * G::A_BYTES + (wid * APW + j_) * 1024);  \
+    } else {                                                                                           \
+      const int p_ = ((i) - 3 * APW) / BPW, j_ = ((i) - 3 * APW) % BPW;                                \
+      SP_GLDS_S(Bblk + p_ * b_img + kb_, b_off[j_],                                                    \
+                st_ + 3 * G::A_BYTES + p_ * G::B_BYTES + (wid * BPW + j_) * 1024);                     \
+    }                                                                                                  \
+  } while (0)
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  {
+    const int64_t ka_ = 0, kb_ = 0;
+    const unsigned st_ = s_base;
+#pragma unroll
+    for (int i = 0; i < NPIECES; ++i) GS_PIECE(i);
+  }
+  SP_GLDS_LANDED();
+  __syncthreads();
+
+  // fragments: row (wave tile row + l31 [+ 32 i]), slot lh ^ ((row >> 4) & 1)
+  const int fslot = (lh ^ ((l31 >> 4) & 1)) * 16;
+  const int a_frag = (wm * 128 + l31) * GS_RB + fslot;
+  const int b_frag = 3 * G::A_BYTES + (wn * 64 + l31) * GS_RB + fslot;
+
+  for (int t = 0; t < KT; ++t) {
+    const bool more = t + 1 < KT;
+    const int64_t ka_ = (int64_t)(t + 1) * a_slab, kb_ = (int64_t)(t + 1) * b_slab;
+    const unsigned st_ = s_base + (unsigned)((t + 1) & 1) * G::STAGE_BYTES;
+    const char* st = gs_smem + (t & 1) * G::STAGE_BYTES;
+    gs_bf16x8 af[3][4], bf[3][2];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[p][i] = *(const gs_bf16x8*)(st + p * G::A_BYTES + a_frag + i * 32 * GS_RB);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bf[p][j] = *(const gs_bf16x8*)(st + p * G::B_BYTES + b_frag + j * 32 * GS_RB);
+    }
+    // 48 MFMAs: al bh, ah bl, am bm, am bh, ah bm, ah bh for the 4 x 2 tiles of the wave; a piece of the next
+    // k-tile's request after every fourth
+    int piece = 0;
+#pragma unroll
+    for (int idx = 0; idx < 48; ++idx) {
+      const int term = idx >> 3, i = (idx & 7) >> 1, j = idx & 1;
+      const int pa = term == 0 ? 2 : (term == 2 || term == 3) ? 1 : 0;
+      const int pb = term == 1 ? 2 : (term == 2 || term == 4) ? 1 : 0;
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[pa][i], bf[pb][j], acc[i][j], 0, 0, 0);
+      if (idx % 4 == 3 && piece < NPIECES) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) GS_PIECE(piece);
+        __builtin_amdgcn_sched_barrier(0);
+        ++piece;
+      }
+    }
+    if (more) SP_GLDS_LANDED();
+    __syncthreads();      // tile t+1 has landed and every wave is done reading stage t
+  }
+#undef GS_PIECE
+
+  // ---- epilogue (as sp_gemm_glds_kernel's): C/D layout col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int col = n0 + wn * 64 + j * 32 + l31;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wm * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (row < M && col < N) {
+          float* p = C + (int64_t)row * ldc + col;
+          float v = acc[i][j][r];
+          if (accumulate) v += *p;
+          *p = v;
+        }
+      }
+    }
+  }
+}
+
+// The fp32 kernel behind the flag: sp_gemm_glds_kernel's body, run only when an operand left the window.
+template <typename Cfg, int BM, int BN, int WM, int WN, int WGS>
+__global__ __launch_bounds__(Cfg::THREADS, WGS) void sp_gemm_f32_gated_kernel(
+    const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, float* __restrict__ C,
+    int64_t ldc, int M, int N, int K, int accumulate, int tiles_m, int tiles_n, const unsigned* __restrict__ flag) {
+  if (*flag == 0u) return;
+  sp_gemm_glds_body<Cfg, BM, BN, WM, WN>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, tiles_m, tiles_n);
+}
+
+// ---- plan ---------------------------------------------------------------------------------------------------------
+// Whether the tier is taken.  It is where the fp32 tier would run the data-parallel 256 x 128 direct-to-LDS kernel (so
+// that the gated fallback reproduces it bit for bit) on at least one full round of tiles, the images fit under
+// GS_IMAGE_CAP, and a cost model says the cut passes are amortised: the cut moves 10 bytes per operand element at the
+// streaming rate, and the mainloop runs ceil(tiles / slots) rounds of 6 bf16 products at the rate the k-means split
+// kernel sustains (1.1e15 issued flop/s); the fp32 tier is priced as in sp_sk_plan.
+// SP_GEMM_SPLIT=0 (read once) keeps the fp32 tier everywhere.
+#define GS_CUT_BYTES_PER_S 3.0e12
+#define GS_ISSUED_FLOPS 1.1e15
+static bool sp_gemm_bf16_plan(int64_t M, int64_t N, int64_t K) {
+  static int mode = -2;
+  if (mode == -2) {
+    const char* e = getenv("SP_GEMM_SPLIT");
+    mode = e ? atoi(e) : 1;
+  }
+  using G = GsCfg<GS_WN>;
+  if (mode == 0 || K < 16 || N % 4 != 0 || N < 4 || M < 1 || M > 2147483647LL || N > 2147483647LL || K > 2147483647LL)
+    return false;
+  const int64_t tb = ((M + 255) / 256) * ((N + 127) / 128);
+  if (tb < 2 * SP_CUS || tb >= 2147483647LL) return false;    // the 256 x 128 tiles do not fill the chip
+  double dp_cost;
+  if (sp_gemm_dp_choice(M, N, &dp_cost) != 6 || sp_sk_plan(M, N, K)) return false;
+  const int64_t KT = (K + GS_BK - 1) / GS_BK;
+  if ((double)KT * 3.0 * GS_RB * ((double)M + (double)N) > (double)GS_IMAGE_CAP) return false;
+  const double fp32_s = dp_cost * 128.0 * 128.0 * (double)K * 2.0 / (157.3e12 * 0.95 / SP_CUS);
+  const int64_t tiles = ((M + G::BM - 1) / G::BM) * ((N + G::BN - 1) / G::BN);
+  const int64_t rounds = (tiles + G::SLOTS - 1) / G::SLOTS;
+  const double main_s = (double)rounds * G::SLOTS * (6.0 * 2.0 * G::BM * G::BN * (double)K) / GS_ISSUED_FLOPS;
+  const double cut_s = 10.0 * ((double)M + (double)N) * (double)K / GS_CUT_BYTES_PER_S;
+  return (main_s + cut_s + 20e-6) < 0.92 * fp32_s;
+}
+
+static size_t sp_gemm_bf16_ws_bytes(int64_t M, int64_t N, int64_t K) {
+  return GS_WS_HEAD + (size_t)((K + GS_BK - 1) / GS_BK) * 3 * GS_RB * (size_t)(M + N);
+}
+
+static int sp_gemm_bf16_launch(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
+                               int64_t N, int64_t K, int acc, void* ws, hipStream_t st) {
+  using G = GsCfg<GS_WN>;
+  char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  unsigned* flag = (unsigned*)base;
+  const int64_t KT = (K + GS_BK - 1) / GS_BK;
+  const int64_t a_img = KT * M * GS_RB, b_img = KT * N * GS_RB;       // bytes
+  char* Aimg = base + 256;
+  char* Bimg = Aimg + 3 * a_img;
+  const int64_t tiles_m = (M + G::BM - 1) / G::BM, tiles_n = (N + G::BN - 1) / G::BN;
+  auto kern = sp_gemm_glds_kernel_bf16x3<GS_WN>;
+  using FCfg = GldsCfg<256, 128, 2, 2>;
+  auto gated = sp_gemm_f32_gated_kernel<FCfg, 256, 128, 2, 2, 2>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    SP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM_BYTES));
+    SP_HIP(hipFuncSetAttribute((const void*)gated, hipFuncAttributeMaxDynamicSharedMemorySize, FCfg::LDS_BYTES));
+    attr_set = true;
+  }
+  SP_HIP(hipMemsetAsync(flag, 0, 256, st));
+  hipLaunchKernelGGL(sp_gemm_cut_rows_kernel, dim3((unsigned)((M + 31) / 32), (unsigned)((K + 255) / 256)), dim3(256), 0, st,
+                     A, lda, (int)M, (int)K, (__bf16*)Aimg, a_img / 2, flag);
+  hipLaunchKernelGGL(sp_gemm_cut_cols_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)KT), dim3(256), 0, st, B, ldb,
+                     (int)N, (int)K, (__bf16*)Bimg, b_img / 2, flag);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(G::THREADS), G::SMEM_BYTES, st, (const char*)Aimg,
+                     a_img, (const char*)Bimg, b_img, C, ldc, (int)M, (int)N, (int)KT, acc, (int)tiles_m, (int)tiles_n,
+                     (const unsigned*)flag);
+  const int64_t ftm = (M + 255) / 256, ftn = (N + 127) / 128;
+  hipLaunchKernelGGL(gated, dim3((unsigned)(ftm * ftn)), dim3(FCfg::THREADS), FCfg::LDS_BYTES, st, A, lda, B, ldb, C, ldc,
+                     (int)M, (int)N, (int)K, acc, (int)ftm, (int)ftn, (const unsigned*)flag);
+  SP_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace

@@ -139,7 +139,8 @@ def gemm_f32(a, b, c, accumulate=False):
   K2, N = b.shape
   assert K == K2 and tuple(c.shape) == (M, N), (a.shape, b.shape, c.shape)
   assert a.stride(1) == 1 and b.stride(1) == 1 and c.stride(1) == 1
-  need = lib.sp_gemm_workspace_bytes(dt, M, N, K)     # > 0: few output tiles, long contraction -> split-K
+  need = max(lib.sp_gemm_workspace_bytes(dt, M, N, K),         # > 0: few output tiles, long contraction -> split-K
+             lib.sp_gemm_split_workspace_bytes(dt, M, N, K))   # > 0: the operand images of the bf16 split tier
   ws = _ws.get(need, a.device) if need else None
   check(lib.sp_gemm_ws(dt, C.c_void_p(a.data_ptr()), a.stride(0) if M > 1 else max(K, 1),
                        C.c_void_p(b.data_ptr()), b.stride(0) if K > 1 else max(N, 1),
