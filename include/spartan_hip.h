@@ -43,7 +43,12 @@ enum sp_dtype {
   SP_I64 = 3,
   SP_BOOL = 4, /* numpy bool_: one byte, 0/1 */
   SP_U8 = 5,
-  SP_DTYPE_COUNT = 6
+  SP_I8 = 6,
+  SP_I16 = 7,
+  SP_U16 = 8,
+  SP_U32 = 9,
+  SP_F16 = 10, /* IEEE binary16; evaluated in the float class (every half is a float), rounded once at the store */
+  SP_DTYPE_COUNT = 11
 };
 
 /* ---- fused LocalExpr program --------------------------------------------
@@ -108,7 +113,13 @@ enum sp_opcode {
   SP_OP_NORM_CDF = 41, /* standard normal CDF, 0.5 * erfc(-x / sqrt(2)) (statistics.py:224-225) */
   /* ternary: dst = a ? b : c */
   SP_OP_WHERE = 45,
-  /* dtype normalisation inside a wider class */
+  /* dtype normalisation inside a wider class.  The instruction's `c` field (unused by these operators otherwise)
+   * selects the width; 0 is the type the name says:
+   *   TO_F32  c = 0 float32, 1 float16 (rounded to the nearest half, ties to even, ONCE from the class type -- a
+   *           double does not pass through float -- and kept as a value of the class)
+   *   TO_I32  c = 0 int32,   1 int8,   2 int16   (floats: the int32 conversion, then wrapped)
+   *   TO_U8   c = 0 uint8,   1 uint16, 2 uint32  (floats: the int32 conversion, for uint32 the int64 one, then wrapped)
+   * Two programs that differ in the selector alone are different programs for every tier. */
   SP_OP_TO_F32 = 50,  /* round to float32 */
   SP_OP_TO_I32 = 51,  /* C cast to int32 (wraps / truncates toward zero) */
   SP_OP_TO_I64 = 52,  /* truncate toward zero */
@@ -273,7 +284,7 @@ int sp_update(void* d_dst, int32_t dst_dtype, const int64_t* dst_shape, int32_t 
               const int64_t* ul, const int64_t* lr, const void* d_src, int32_t src_dtype,
               int32_t reducer, int32_t mask_mode, uint8_t* d_mask, void* stream);
 
-/* sp_slice_copy: strided <=4-d box copy (element size 1/4/8 bytes) used by
+/* sp_slice_copy: strided <=4-d box copy (element size 1/2/4/8 bytes) used by
  * DistArrayImpl.fetch's stitch `tgt[dst_slice] = result`
  * (spartan/array/distarray.py:355-365), Tile.get(subslice) (tile.pyx:64-113)
  * and sparse.multiple_slice's dense branch (sparse.pyx:297-301).
@@ -522,7 +533,8 @@ int sp_tiling_solve(int32_t n_nodes, int64_t n_edges, const int32_t* edge_u, con
                     int32_t* choice, double* total);
 
 /* sp_gather_rows: dst[i, :] = src[idx[i], :] -- integer-array indexing `x[idx]`, the tile body of _int_index_mapper
- * (spartan/expr/operator/filter.py:50-75).  Rows of row_bytes bytes (a multiple of 4), source rows
+ * (spartan/expr/operator/filter.py:50-75).  Rows of row_bytes bytes (a multiple of 4, or of 2 for rows of 2-byte
+ * elements), source rows
  * src_row_stride_bytes apart; idx int64 on the device, negative values count from the end. */
 int sp_gather_rows(const void* d_src, int64_t src_row_stride_bytes, int64_t n_src_rows, const int64_t* d_idx,
                    int64_t n_idx, int64_t row_bytes, void* d_dst, void* stream);
@@ -590,7 +602,9 @@ int sp_blob_slice_copy(uint64_t dst, const int64_t* dst_ul, uint64_t src, const 
  * Rendezvous: rank 0 calls sp_comm_unique_id and hands the SP_COMM_UID_BYTES token to every rank by whatever
  * channel the host has (the reference's workers register with the master over TCP, worker.py:98-124); every
  * rank then calls sp_comm_init with the device it computes on current.  reducer: enum sp_reducer (ADD MUL MAX
- * MIN; AND / OR for SP_BOOL).  All calls are asynchronous on `stream`; RCCL is bound at run time
+ * MIN; AND / OR for SP_BOOL); SP_I16 / SP_U16 have no RCCL type: they travel in the copy collectives
+ * (all-gather, broadcast, all-to-all: by byte size) and are refused, with the reason, by the reducing ones.  All
+ * calls are asynchronous on `stream`; RCCL is bound at run time
  * (sp_comm_available() == 0 when the host has none): $SPARTAN_RCCL_LIB, then the librccl.so.1 installed beside the
  * HIP runtime this library is bound to, then the loader's search path.  A copy linked against ANOTHER HIP runtime
  * than this library's (a process can hold two) is refused with the reason in sp_last_error(): the pointers,

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SPARTAN_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libspartan_hip.so')
 
 # ---- enums (mirror include/spartan_hip.h) ---------------------------------
-SP_F32, SP_F64, SP_I32, SP_I64, SP_BOOL, SP_U8 = range(6)
+SP_F32, SP_F64, SP_I32, SP_I64, SP_BOOL, SP_U8, SP_I8, SP_I16, SP_U16, SP_U32, SP_F16 = range(11)
 SP_LINK_IDENTITY, SP_LINK_EXP_RATIO, SP_LINK_SIGMOID = range(3)     # sp_rowdot_link_colsum_f32
 SP_MAX_INPUTS, SP_MAX_INSTR, SP_MAX_CONSTS, SP_MAX_DIMS, SP_NREG = 8, 64, 16, 4, 8
 SP_BLOB_MAX_DIMS, SP_COMM_UID_BYTES = 8, 128
@@ -36,7 +36,13 @@ NEAREST_AUTO, NEAREST_EXACT, NEAREST_FUSED, NEAREST_FUSED_UNCHECKED, NEAREST_SPL
 _NP2SP = {
     np.dtype(np.float32): SP_F32, np.dtype(np.float64): SP_F64, np.dtype(np.int32): SP_I32,
     np.dtype(np.int64): SP_I64, np.dtype(np.bool_): SP_BOOL, np.dtype(np.uint8): SP_U8,
+    np.dtype(np.int8): SP_I8, np.dtype(np.int16): SP_I16, np.dtype(np.uint16): SP_U16,
+    np.dtype(np.uint32): SP_U32, np.dtype(np.float16): SP_F16,
 }
+# the narrow element types: exact in an arithmetic class, so load / store conversions of the tile kernels only;
+# the whole-tile kernels outside the fused path (GEMM, sort, scan, random fill, sparse, k-means) do not take them
+NARROW = frozenset(np.dtype(t) for t in (np.int8, np.int16, np.uint16, np.uint32, np.float16))
+SUPPORTED = 'float32 float64 int32 int64 bool uint8 int8 int16 uint16 uint32 float16'
 _SP2NP = {v: k for k, v in _NP2SP.items()}
 
 
@@ -44,12 +50,20 @@ def sp_dtype(dt):
   dt = np.dtype(dt)
   if dt not in _NP2SP:
     raise TypeError('dtype %s is not supported by the HIP tile backend '
-                    '(supported: float32 float64 int32 int64 bool uint8)' % dt)
+                    '(supported: %s)' % (dt, SUPPORTED))
   return _NP2SP[dt]
 
 
 def np_dtype(code):
   return _SP2NP[code]
+
+
+def refuse_narrow(dt, what):
+  """The loud refusal of a kernel outside the fused tile path that is handed one of the narrow element types."""
+  dt = np.dtype(dt)
+  if dt in NARROW:
+    raise TypeError('dtype %s is not supported by %s of the HIP tile backend (supported: float32 float64 int32 int64 '
+                    'bool uint8 where the kernel takes them); convert with astype first' % (dt, what))
 
 
 class sp_instr(C.Structure):

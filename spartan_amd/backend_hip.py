@@ -561,6 +561,7 @@ class HipBackend(object):
   def random_tile(self, kind, shape, dtype, low=0, high=10):
     """One srandom tile (srandom.py:38-50) from the counter-based generator; consecutive
     fills consume consecutive counters of this worker's stream."""
+    _hip.refuse_narrow(dtype, 'the random builders')
     out = self.empty(shape, dtype)
     n = out.numel()
     if n:
@@ -958,6 +959,8 @@ class HipBackend(object):
     if tile.is_sparse_blob(a) or tile.is_sparse_blob(b):
       return self._sparse_dot(a, b)
     a_dt, b_dt = self.dtype_of(a), self.dtype_of(b)
+    for dt in (a_dt, b_dt):
+      _hip.refuse_narrow(dt, 'dot')
     res_dt = np.result_type(a_dt, b_dt)
     if a.dim() == 2 and b.dim() == 2 and b.shape[1] == 1:
       # (M,K).(K,1), the lreg `X.w` (linear_regression.py:10-16): HBM-bound matrix.vector,
@@ -1125,7 +1128,9 @@ class HipBackend(object):
   def sort_axis(self, t, axis, indices=False):
     """np.sort(t, axis) / np.argsort(t, axis, kind='stable') of a tile (sort.py:68-69, :137-138): the axis is
     brought last by a strided copy, sp_sort_rows sorts every line, and the result is copied back."""
-    t = self.contiguous(self._as_device(t))
+    t = self._as_device(t)
+    _hip.refuse_narrow(self.dtype_of(t), 'sort')
+    t = self.contiguous(t)
     shape = tuple(t.shape)
     nd = len(shape)
     axis = axis if axis >= 0 else axis + nd
@@ -1189,6 +1194,7 @@ class HipBackend(object):
 
   def cumscan(self, t, axis, product=False):
     """np.cumsum / np.cumprod along `axis` (sp_cumscan)."""
+    _hip.refuse_narrow(self.dtype_of(t), 'scan (cumsum / cumprod)')
     t = self.contiguous(t)
     if self.dtype_of(t) == np.bool_:
       t = self.astype(t, np.int64)

@@ -54,6 +54,8 @@ int sp_validate_program(const sp_program* p) {
       if (I.op == SP_OP_WHERE) reads |= 1u << I.c;
       if (reads & ~defined) SP_FAIL("instr %d: reads a register nothing has written", i);
     }
+    if ((I.op == SP_OP_TO_F32 && I.c > 1) || ((I.op == SP_OP_TO_I32 || I.op == SP_OP_TO_U8) && I.c > 2))
+      SP_FAIL("instr %d: width selector %d out of range", i, (int)I.c);
     if (I.op != SP_OP_NOP) defined |= 1u << I.dst;
   }
   if (!(defined & (1u << p->result_reg))) SP_FAIL("result_reg=%d is never written", p->result_reg);
@@ -167,6 +169,50 @@ static int sp_map_go_jit(const sp_program* p, const sp_inputs& in, void* out, in
   return 0;
 }
 
+// Dense programs with a 1- or 2-byte operand or output: U adjacent groups per lane (sp_map_kernel_wide), run-time
+// specialised with U = 4 for large tiles, interpreted with U = 2.  *handled stays false when the tile is shorter than
+// one run of U * V elements.
+static bool sp_has_narrow(const sp_program* p) {
+  if (sp_is_narrow(p->out_dtype) && p->out_dtype != SP_BOOL) return true;
+  for (int j = 0; j < p->n_inputs; ++j)
+    if (sp_is_narrow(p->in_dtype[j]) && p->in_stride[j][p->ndim - 1] != 0) return true;
+  return false;
+}
+template <typename T>
+static int sp_map_go_wide(const sp_program* p, const sp_inputs& in, void* out, int64_t n, hipStream_t st,
+                          bool* handled) {
+  constexpr int V = sp_cls<T>::V, UJ = 4, UI = 2;
+  *handled = false;
+  int64_t done = 0;
+  if (sp_jit_enabled() && p->n_instr != 0 && n >= sp_jit_min_elems() && n / (V * UJ) > 0) {
+    char expr[176];
+    snprintf(expr, sizeof(expr), "sp_map_kernel_wide<%s, %d, %d, StaticProg<1000>, %d>", sp_cls<T>::name(), V, UJ,
+             (p->pad & SP_PAD_STREAM) ? 1 : 0);
+    void* fn = sp_jit_get("map_kernel.hpp", expr, p);
+    if (fn) {
+      int64_t nvec = n / (V * UJ), start = 0;
+      int64_t blocks = (nvec + SP_BLOCK - 1) / SP_BLOCK;
+      if (blocks > (1LL << 30)) blocks = 1LL << 30;
+      sp_program pc = *p;
+      sp_inputs ic = in;
+      void* args[] = {&pc, &ic, &out, &start, &nvec};
+      if (sp_jit_launch(fn, dim3((unsigned)blocks), dim3(SP_BLOCK), args, st)) return 1;
+      done = nvec * V * UJ;
+    }
+  }
+  if (!done) {
+    const int64_t nvec = n / (V * UI);
+    if (!nvec) return 0;
+    hipLaunchKernelGGL((sp_map_kernel_wide<T, V, UI>), dim3(sp_grid_for(nvec, 1)), dim3(SP_BLOCK), 0, st, *p, in, out,
+                       (int64_t)0, nvec);
+    SP_CHECK_LAUNCH();
+    done = nvec * V * UI;
+  }
+  *handled = true;
+  if (n - done && sp_map_go<T, 1, 1, true>(p, in, out, done, n - done, st)) return 1;
+  return 0;
+}
+
 template <typename T, int V, bool LINEAR>
 static int sp_map_go_u(const sp_program* p, const sp_inputs& in, void* out, int64_t start, int64_t nvec,
                        hipStream_t st) {
@@ -197,6 +243,11 @@ static int sp_map_launch(const sp_program* p, const sp_inputs& in, const void* c
         if (n - nmain && sp_map_go<T, 1, 1, true>(p, in, out, nmain, n - nmain, st)) return 1;
         return 0;
       }
+    }
+    if (sp_has_narrow(p)) {
+      bool handled = false;
+      if (sp_map_go_wide<T>(p, in, out, n, st, &handled)) return 1;
+      if (handled) return 0;
     }
     if (nmain) {
       bool handled = false;

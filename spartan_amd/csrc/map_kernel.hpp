@@ -147,3 +147,37 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_map_kernel(const sp_program p, co
   }
 }
 
+
+// The dense map for programs with 1- or 2-byte operands or output: a lane evaluates U ADJACENT groups of V elements, so
+// that such an operand is one access of U * V elements per lane (see sp_is_narrow, sp_interp.hpp).  `nvec` counts
+// those U * V-element runs; the host hands the last n % (U * V) elements to the scalar kernel.  Same signature as
+// sp_map_kernel.  U = 4 for run-time specialised programs, 2 for the interpreter (four register files do not fit).
+template <typename T, int V, int U, typename P = DynProg, int NTM = 0>
+__global__ __launch_bounds__(SP_BLOCK) void sp_map_kernel_wide(const sp_program p, const sp_inputs in,
+                                                               void* __restrict__ out, int64_t start, int64_t nvec) {
+  const int64_t stride = (int64_t)gridDim.x * SP_BLOCK;
+  const sp_dyn dyn = sp_dyn_program<P, T>(p);
+  const bool wide_out = sp_is_narrow(p.out_dtype) && p.out_dtype != SP_BOOL;
+  for (int64_t i = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x; i < nvec; i += stride) {
+    int64_t L[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) L[u] = start + (i * U + u) * V;
+    T res[U][V];
+    sp_eval_u<T, V, U, true, P, NTM, sp_no_ahead, sp_no_ahead, true>(p, in, L, res, nullptr, dyn);
+    if (wide_out) {
+      T all[U * V];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) all[u * V + v] = res[u][v];
+      if (SP_STREAMS(NTM, p)) sp_store_narrow_any<T, U * V, true>(out, p.out_dtype, L[0], all);
+      else sp_store_narrow_any<T, U * V, false>(out, p.out_dtype, L[0], all);
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (SP_STREAMS(NTM, p)) sp_store_vec<T, V, true>(out, p.out_dtype, L[u], res[u]);
+        else sp_store_vec<T, V>(out, p.out_dtype, L[u], res[u]);
+      }
+    }
+  }
+}

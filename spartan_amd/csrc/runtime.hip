@@ -481,8 +481,21 @@ struct Comm {
     }                                                                                      \
   } while (0)
 
-int nccl_dtype(int32_t dt, ncclDataType_t* out) {
+// `scale` (copy collectives): the type has no RCCL name -- int16, uint16 -- and travels as that many bytes per
+// element; a reducing collective passes none and refuses such a type with the reason.
+int nccl_dtype(int32_t dt, ncclDataType_t* out, int64_t* scale = nullptr) {
+  if (scale) *scale = 1;
   switch (dt) {
+    case SP_I8: *out = ncclInt8; return 0;
+    case SP_U32: *out = ncclUint32; return 0;
+    case SP_F16: *out = ncclFloat16; return 0;
+    case SP_I16:
+    case SP_U16:
+      if (!scale) SP_FAIL("collective: RCCL has no 16-bit integer type, so %s tiles cannot be reduced across ranks "
+                          "(astype(int32) first)", dt == SP_I16 ? "int16" : "uint16");
+      *out = ncclUint8;
+      *scale = 2;
+      return 0;
     case SP_F32: *out = ncclFloat32; return 0;
     case SP_F64: *out = ncclFloat64; return 0;
     case SP_I32: *out = ncclInt32; return 0;
@@ -628,19 +641,21 @@ extern "C" int sp_comm_all_gather(void* comm, const void* d_src, void* d_dst, in
                                   void* stream) {
   if (!comm) SP_FAIL("sp_comm_all_gather: NULL communicator");
   ncclDataType_t dt;
-  if (nccl_dtype(dtype, &dt)) return 1;
+  int64_t scale;
+  if (nccl_dtype(dtype, &dt, &scale)) return 1;
   if (send_count == 0) return 0;
-  SP_NCCL(g_rccl.AllGather(d_src, d_dst, (size_t)send_count, dt, as_comm(comm)->comm, (hipStream_t)stream));
+  SP_NCCL(g_rccl.AllGather(d_src, d_dst, (size_t)(send_count * scale), dt, as_comm(comm)->comm, (hipStream_t)stream));
   return 0;
 }
 
 extern "C" int sp_comm_bcast(void* comm, void* d_buf, int64_t count, int32_t dtype, int32_t root, void* stream) {
   if (!comm) SP_FAIL("sp_comm_bcast: NULL communicator");
   ncclDataType_t dt;
-  if (nccl_dtype(dtype, &dt)) return 1;
+  int64_t scale;
+  if (nccl_dtype(dtype, &dt, &scale)) return 1;
   if (root < 0 || root >= as_comm(comm)->world) SP_FAIL("sp_comm_bcast: root %d", root);
   if (count == 0) return 0;
-  SP_NCCL(g_rccl.Broadcast(d_buf, d_buf, (size_t)count, dt, root, as_comm(comm)->comm, (hipStream_t)stream));
+  SP_NCCL(g_rccl.Broadcast(d_buf, d_buf, (size_t)(count * scale), dt, root, as_comm(comm)->comm, (hipStream_t)stream));
   return 0;
 }
 

@@ -38,7 +38,7 @@ void sp_set_error(const char* fmt, ...);
     }                                                                             \
   } while (0)
 
-static inline size_t sp_dtype_size(int32_t dt) {
+__host__ __device__ static inline size_t sp_dtype_size(int32_t dt) {
   switch (dt) {
     case SP_F32: return 4;
     case SP_F64: return 8;
@@ -46,6 +46,11 @@ static inline size_t sp_dtype_size(int32_t dt) {
     case SP_I64: return 8;
     case SP_BOOL: return 1;
     case SP_U8: return 1;
+    case SP_I8: return 1;
+    case SP_I16: return 2;
+    case SP_U16: return 2;
+    case SP_U32: return 4;
+    case SP_F16: return 2;
     default: return 0;
   }
 }

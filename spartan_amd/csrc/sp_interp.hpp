@@ -19,6 +19,10 @@ template <typename T> struct sp_is_integral { static constexpr bool value = fals
 template <> struct sp_is_integral<int64_t> { static constexpr bool value = true; };
 template <> struct sp_is_integral<int32_t> { static constexpr bool value = true; };
 template <> struct sp_is_integral<uint8_t> { static constexpr bool value = true; };
+template <> struct sp_is_integral<int8_t> { static constexpr bool value = true; };
+template <> struct sp_is_integral<int16_t> { static constexpr bool value = true; };
+template <> struct sp_is_integral<uint16_t> { static constexpr bool value = true; };
+template <> struct sp_is_integral<uint32_t> { static constexpr bool value = true; };
 
 template <typename T>
 struct sp_cls;
@@ -98,6 +102,54 @@ __device__ __forceinline__ T sp_cvt(S x) {
   else return (T)x;
 }
 
+// ---- the narrow element types (int8, int16, uint16, uint32, float16) ----
+// Every one of them is exact in its arithmetic class (integers: int64; a half is a float), so they exist as load and
+// store conversions only.  A value of the class type T converted to float16: rounded to nearest even ONCE, as NumPy's
+// astype does -- float -> half is one instruction; a double goes through the float that round-to-odd gives (truncated
+// toward zero, lowest bit set when anything was lost: 13 more bits than a half keeps, so the second rounding sees
+// exactly what the first would have), never through the nearest float, which moves values that lie just beside a
+// tie of two halves onto it; an int64 goes through the nearest float as NumPy's does (every integer below the
+// overflow threshold 65520 is a float).  Subnormal halves are kept by both conversions (the f16 denormal mode is on).
+template <typename T>
+__device__ __forceinline__ _Float16 sp_to_half(T x) {
+  if constexpr (sp_is_same<T, double>::value) {
+    float f = (float)x;
+    if ((double)f != x && f - f == 0.0f) {   // inexact and finite
+      uint32_t b = __builtin_bit_cast(uint32_t, f);
+      if (__builtin_fabs((double)f) > __builtin_fabs(x)) b -= 1u;   // rounded away from zero: one step back
+      f = __builtin_bit_cast(float, b | 1u);
+    }
+    return (_Float16)f;
+  } else {
+    return (_Float16)(float)x;
+  }
+}
+// ... and kept as a value of the class (SP_OP_TO_F32 with selector 1)
+template <typename T>
+__device__ __forceinline__ T sp_round_f16(T x) {
+  const float h = (float)sp_to_half<T>(x);
+  if constexpr (sp_is_integral<T>::value) return (T)sp_f2i64(h);
+  else return (T)h;
+}
+// a value of the class type T as the storage type E.  int8 / int16 / uint16 take the int32 conversion and wrap, as
+// uint8 does; uint32 takes the int64 one (x86-64 has no unsigned conversion: cvttss2si on a 64-bit register).
+template <typename E, typename T>
+__device__ __forceinline__ E sp_to_elem(T x) {
+  if constexpr (sp_is_same<E, _Float16>::value) return sp_to_half<T>(x);
+  else if constexpr (sp_is_same<E, uint32_t>::value) return (E)sp_to_int<int64_t>(x);
+  else return (E)sp_to_int<int32_t>(x);
+}
+// ... and kept as a value of the class (SP_OP_TO_I32 / SP_OP_TO_U8 with a width selector)
+template <typename E, typename T>
+__device__ __forceinline__ T sp_wrap_to(T x) {
+  return (T)sp_to_elem<E, T>(x);
+}
+template <typename T, typename E>
+__device__ __forceinline__ T sp_from_elem(E x) {
+  if constexpr (sp_is_same<E, _Float16>::value) return sp_cvt<T>((float)x);
+  else return (T)x;
+}
+
 // ---- typed loads: `n` consecutive elements (n == V, or 1) converted to T ----
 // NT: the operand is read exactly once by the whole launch (no broadcast dimension), so its lines need not stay in
 // L2: non-temporal vector loads (`global_load_dwordx4 ... nt`).  On the 2 GiB tile this is worth 6.0 -> 6.6-6.8 TB/s
@@ -117,9 +169,29 @@ __device__ __forceinline__ void sp_nt_mark() { asm volatile(""); }
   })                                                                       \
       : *(const TYPE*)(ptr))
 
+// N consecutive elements of a 1- or 2-byte type E (or uint32) in ONE access of N * sizeof(E) bytes, element-aligned
+template <typename T, typename E, int N, bool NT>
+__device__ __forceinline__ void sp_load_narrow(const void* base, int64_t off, T* dst) {
+  const E* p = (const E*)base + off;
+  if constexpr (N == 1) {
+    dst[0] = sp_from_elem<T, E>(p[0]);
+  } else {
+    typedef E vec_t __attribute__((ext_vector_type(N)));
+    typedef vec_t vecu_t __attribute__((aligned(sizeof(E))));
+    const vecu_t v = SP_VLD(vecu_t, p);
+#pragma unroll
+    for (int j = 0; j < N; ++j) dst[j] = sp_from_elem<T, E>(v[j]);
+  }
+}
+
 template <typename T, int N, bool NT = false>
 __device__ __forceinline__ void sp_load_vec(const void* base, int32_t dt, int64_t off, T* dst) {
   switch (dt) {
+    case SP_I8: sp_load_narrow<T, int8_t, N, NT>(base, off, dst); break;
+    case SP_I16: sp_load_narrow<T, int16_t, N, NT>(base, off, dst); break;
+    case SP_U16: sp_load_narrow<T, uint16_t, N, NT>(base, off, dst); break;
+    case SP_U32: sp_load_narrow<T, uint32_t, N, NT>(base, off, dst); break;
+    case SP_F16: sp_load_narrow<T, _Float16, N, NT>(base, off, dst); break;
     case SP_F32: {
       const float* p = (const float*)base + off;
       if constexpr (N == 4) {
@@ -191,9 +263,30 @@ __device__ __forceinline__ void sp_load_vec(const void* base, int32_t dt, int64_
     if constexpr (NT) { sp_nt_mark(); __builtin_nontemporal_store(v_, (TYPE*)(ptr)); sp_nt_mark(); } \
     else *(TYPE*)(ptr) = v_;                                          \
   } while (0)
+template <typename T, typename E, int N, bool NT>
+__device__ __forceinline__ void sp_store_narrow(void* base, int64_t off, const T* src) {
+  E* p = (E*)base + off;
+  if constexpr (N == 1) {
+    p[0] = sp_to_elem<E, T>(src[0]);
+  } else {
+    typedef E vec_t __attribute__((ext_vector_type(N)));
+    typedef vec_t vecu_t __attribute__((aligned(sizeof(E))));
+    vec_t v;
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = sp_to_elem<E, T>(src[j]);
+    if constexpr (NT) { sp_nt_mark(); __builtin_nontemporal_store((vecu_t)v, (vecu_t*)p); sp_nt_mark(); }
+    else *(vecu_t*)p = v;
+  }
+}
+
 template <typename T, int N, bool NT = false>
 __device__ __forceinline__ void sp_store_vec(void* base, int32_t dt, int64_t off, const T* src) {
   switch (dt) {
+    case SP_I8: sp_store_narrow<T, int8_t, N, NT>(base, off, src); break;
+    case SP_I16: sp_store_narrow<T, int16_t, N, NT>(base, off, src); break;
+    case SP_U16: sp_store_narrow<T, uint16_t, N, NT>(base, off, src); break;
+    case SP_U32: sp_store_narrow<T, uint32_t, N, NT>(base, off, src); break;
+    case SP_F16: sp_store_narrow<T, _Float16, N, NT>(base, off, src); break;
     case SP_F32: {
       float* p = (float*)base + off;
       if constexpr (N == 4) {
@@ -251,6 +344,45 @@ __device__ __forceinline__ void sp_store_vec(void* base, int32_t dt, int64_t off
       uint8_t* p = (uint8_t*)base + off;
 #pragma unroll
       for (int j = 0; j < N; ++j) p[j] = (uint8_t)sp_to_int<int32_t>(src[j]);
+    } break;
+  }
+}
+
+// ---- wide accesses for 1- and 2-byte elements (dense path) ----
+// V elements of a 1-byte type are a 4-byte access per lane (2 bytes in the int64 class), 256 B per wave instruction
+// where a float lane moves 16 B.  The wide map kernel (sp_map_kernel_wide) gives a lane U ADJACENT groups instead, and
+// an operand or output of a 1- or 2-byte type then moves all U * V elements in one access: 16 int8 or 16 halves
+// (16 / 32 B) with U = 4 in the float class.  Wider types keep one access per group.
+__host__ __device__ __forceinline__ bool sp_is_narrow(int32_t dt) {
+  return dt == SP_BOOL || dt == SP_U8 || dt == SP_I8 || dt == SP_I16 || dt == SP_U16 || dt == SP_F16;
+}
+template <typename T, int N, bool NT>
+__device__ __forceinline__ void sp_load_narrow_any(const void* base, int32_t dt, int64_t off, T* dst) {
+  switch (dt) {
+    case SP_I8: sp_load_narrow<T, int8_t, N, NT>(base, off, dst); break;
+    case SP_I16: sp_load_narrow<T, int16_t, N, NT>(base, off, dst); break;
+    case SP_U16: sp_load_narrow<T, uint16_t, N, NT>(base, off, dst); break;
+    case SP_F16: sp_load_narrow<T, _Float16, N, NT>(base, off, dst); break;
+    default: sp_load_narrow<T, uint8_t, N, NT>(base, off, dst); break;   // SP_U8 / SP_BOOL
+  }
+}
+// (not SP_BOOL: its store is a test against 0, sp_store_vec)
+template <typename T, int N, bool NT>
+__device__ __forceinline__ void sp_store_narrow_any(void* base, int32_t dt, int64_t off, const T* src) {
+  switch (dt) {
+    case SP_I8: sp_store_narrow<T, int8_t, N, NT>(base, off, src); break;
+    case SP_I16: sp_store_narrow<T, int16_t, N, NT>(base, off, src); break;
+    case SP_U16: sp_store_narrow<T, uint16_t, N, NT>(base, off, src); break;
+    case SP_F16: sp_store_narrow<T, _Float16, N, NT>(base, off, src); break;
+    default: {   // SP_U8
+      uint8_t* p = (uint8_t*)base + off;
+      typedef uint8_t vec_t __attribute__((ext_vector_type(N)));
+      typedef vec_t vecu_t __attribute__((aligned(1)));
+      vec_t v;
+#pragma unroll
+      for (int j = 0; j < N; ++j) v[j] = (uint8_t)sp_to_int<int32_t>(src[j]);
+      if constexpr (NT) { sp_nt_mark(); __builtin_nontemporal_store((vecu_t)v, (vecu_t*)p); sp_nt_mark(); }
+      else *(vecu_t*)p = v;
     } break;
   }
 }
@@ -660,11 +792,22 @@ __device__ __forceinline__ void sp_step(const sp_program& p, const sp_instr I, c
 #undef SP_RC
       SP_EACH(av != (T)0 ? bv : c[u][v]);
     } break;
-    case SP_OP_TO_F32: SP_EACH(M::to_f32(av)); break;
-    case SP_OP_TO_I32: SP_EACH(M::to_i32(av)); break;
+    // (the width selector of the narrowing operators is the instruction's c field: see the header)
+    case SP_OP_TO_F32:
+      if (I.c == 1) { SP_EACH(sp_round_f16<T>(av)); } else { SP_EACH(M::to_f32(av)); }
+      break;
+    case SP_OP_TO_I32:
+      if (I.c == 1) { SP_EACH(sp_wrap_to<int8_t>(av)); }
+      else if (I.c == 2) { SP_EACH(sp_wrap_to<int16_t>(av)); }
+      else { SP_EACH(M::to_i32(av)); }
+      break;
     case SP_OP_TO_I64: SP_EACH(M::to_i64(av)); break;
     case SP_OP_TO_BOOL: SP_EACH((T)(av != (T)0)); break;
-    case SP_OP_TO_U8: SP_EACH(M::to_u8(av)); break;
+    case SP_OP_TO_U8:
+      if (I.c == 1) { SP_EACH(sp_wrap_to<uint16_t>(av)); }
+      else if (I.c == 2) { SP_EACH(sp_wrap_to<uint32_t>(av)); }
+      else { SP_EACH(M::to_u8(av)); }
+      break;
     case SP_OP_ADDC: { const T cv = sp_const<T>(p, I.a); SP_EACH(bv + cv); } break;
     case SP_OP_SUBC: { const T cv = sp_const<T>(p, I.a); SP_EACH(bv - cv); } break;
     case SP_OP_RSUBC: { const T cv = sp_const<T>(p, I.a); SP_EACH(cv - bv); } break;
@@ -749,8 +892,10 @@ __device__ __forceinline__ bool sp_ahead_applies(const sp_program& p) {
 // array would be one 32*U-dword alloca and go to scratch).
 // `ahead` / `mid`: see sp_ahead -- the operands come from `ahead`; `mid()` runs once they sit in the register file and
 // before the program does (the caller's place for the next fetch and for the stores it held back).
+// WIDE (dense programs): the U groups are ADJACENT, L[u] == L[0] + u * V, and a dense operand of a 1- or 2-byte type is
+// read for all of them in one access (sp_load_narrow_any).
 template <typename T, int V, int U, bool LINEAR, typename P = DynProg, int NTM = 2, typename AH = sp_no_ahead,
-          typename MID = sp_no_ahead>
+          typename MID = sp_no_ahead, bool WIDE = false>
 __device__ __forceinline__ void sp_eval_u(const sp_program& p, const sp_inputs& in, const int64_t (&L)[U],
                                           T (&out)[U][V], const int64_t (*pre)[2] = nullptr,
                                           const sp_dyn dyn = sp_dyn{0u, false}, AH* ahead = nullptr,
@@ -847,9 +992,22 @@ __device__ __forceinline__ void sp_eval_u(const sp_program& p, const sp_inputs& 
 #undef SP_TAKE
           }
         } else {
+          bool wide = false;
+          if constexpr (WIDE) wide = sp_is_narrow(dt) && p.in_stride[j][p.ndim - 1] != 0;
+          if (wide) {
+            if constexpr (WIDE) {
+              T all[U * V];
+              if (SP_STREAMS(NTM, p)) sp_load_narrow_any<T, U * V, true>(in.p[j], dt, L[0], all);
+              else sp_load_narrow_any<T, U * V, false>(in.p[j], dt, L[0], all);
+#define SP_SPREAD(u) _Pragma("unroll") for (int v = 0; v < V; ++v) r##u[j * V + v] = all[u * V + v];
+              SP_U_LIST(SP_SPREAD)
+#undef SP_SPREAD
+            }
+          } else {
 #define SP_LD(u) sp_load_linear<T, V, NTM>(p, in, j, dt, L[u], &r##u[j * V]);
-          SP_U_LIST(SP_LD)
+            SP_U_LIST(SP_LD)
 #undef SP_LD
+          }
         }
       } else {
         const int64_t inner = p.in_stride[j][p.ndim - 1];
@@ -998,7 +1156,7 @@ static inline int sp_find_static(const sp_program* p, int32_t out_dtype) {
     for (int i = 0; ok && i < S::N; ++i) {                                                    \
       const sp_instr& x = p->instr[i];                                                        \
       const sp_instr y = S::at(i);                                                          \
-      ok = x.op == y.op && x.dst == y.dst && x.a == y.a && (x.op == SP_OP_CONST || x.b == y.b); \
+      ok = x.op == y.op && x.dst == y.dst && x.a == y.a && (x.op == SP_OP_CONST || x.b == y.b) && x.c == y.c; \
     }                                                                                         \
     if (ok) return ID;                                                                        \
   }

@@ -225,7 +225,7 @@ extern "C" int sp_slice_copy(void* d_dst, const int64_t* dst_stride, const void*
                              const int64_t* src_stride, const int64_t* shape, int32_t ndim,
                              int32_t elem_size, void* stream) {
   if (ndim < 0 || ndim > SP_MAX_DIMS) SP_FAIL("sp_slice_copy: ndim=%d unsupported (max %d)", ndim, SP_MAX_DIMS);
-  if (elem_size != 1 && elem_size != 4 && elem_size != 8) SP_FAIL("sp_slice_copy: elem_size=%d", elem_size);
+  if (elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8) SP_FAIL("sp_slice_copy: elem_size=%d", elem_size);
   if (!d_dst || !d_src) SP_FAIL("sp_slice_copy: NULL pointer");
   BoxDesc b;
   memset(&b, 0, sizeof(b));
@@ -247,14 +247,17 @@ extern "C" int sp_slice_copy(void* d_dst, const int64_t* dst_stride, const void*
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   // 2-D transpose pattern (dst dense rows, src walks a column): LDS-tiled kernel
-  if (b.ndim == 2 && (elem_size == 4 || elem_size == 8) && b.dstride[1] == 1 && b.sstride[0] == 1 &&
+  if (b.ndim == 2 && (elem_size == 2 || elem_size == 4 || elem_size == 8) && b.dstride[1] == 1 && b.sstride[0] == 1 &&
       b.sstride[1] >= b.shape[0] && b.dstride[0] >= b.shape[1] && b.shape[0] >= 16 && b.shape[1] >= 16) {
     // dst[i][j] = src[j][i] with src row-major of leading dimension sstride[1]
     const int64_t R = b.shape[1], Cc = b.shape[0];   // src is R x Cc
     int64_t blocks = ((R + 63) / 64) * ((Cc + 63) / 64);
     const int64_t cap = (int64_t)SP_CUS * SP_BLOCKS_PER_CU * 4;
     if (blocks > cap) blocks = cap;
-    if (elem_size == 4)
+    if (elem_size == 2)
+      hipLaunchKernelGGL((sp_transpose_kernel<uint16_t>), dim3((unsigned)blocks), dim3(SP_BLOCK), 0, st,
+                         (uint16_t*)d_dst, (const uint16_t*)d_src, R, Cc, b.sstride[1], b.dstride[0]);
+    else if (elem_size == 4)
       hipLaunchKernelGGL((sp_transpose_kernel<uint32_t>), dim3((unsigned)blocks), dim3(SP_BLOCK), 0, st,
                          (uint32_t*)d_dst, (const uint32_t*)d_src, R, Cc, b.sstride[1], b.dstride[0]);
     else
@@ -292,6 +295,9 @@ extern "C" int sp_slice_copy(void* d_dst, const int64_t* dst_stride, const void*
     case 4:
       hipLaunchKernelGGL((sp_box_copy_kernel<uint32_t>), g, blk, 0, st, (uint32_t*)d_dst, (const uint32_t*)d_src, b, n);
       break;
+    case 2:
+      hipLaunchKernelGGL((sp_box_copy_kernel<uint16_t>), g, blk, 0, st, (uint16_t*)d_dst, (const uint16_t*)d_src, b, n);
+      break;
     default:
       hipLaunchKernelGGL((sp_box_copy_kernel<uint8_t>), g, blk, 0, st, (uint8_t*)d_dst, (const uint8_t*)d_src, b, n);
       break;
@@ -307,6 +313,7 @@ struct UpdDesc {
   int64_t dstride[SP_MAX_DIMS];  // element strides of the tile
   int64_t doff;                  // element offset of the box origin in the tile
   int32_t dst_dtype, src_dtype, reducer, mask_mode;
+  int32_t round_f16;             // NumPy reduces in float16: the reduced value is rounded to half before the astype
 };
 
 template <typename T>
@@ -324,7 +331,9 @@ __device__ __forceinline__ T sp_apply_reducer(int r, T old, T upd) {
 
 // T = the type NumPy computes reducer(old, update) in (sp_merge_class): float / double, or int64 for two integer /
 // bool operands -- wider than their promoted type, which the store's wrap to the tile's width makes invisible except
-// for a bool tile, whose value is the reduced one wrapped to the update's width, then tested against 0.  The result
+// for a bool tile, whose value is the reduced one wrapped to the update's width, then tested against 0.  Where NumPy
+// reduces in float16 (a half next to a half, an 8-bit integer or a bool) T is float and the reduced value is rounded
+// to half (UpdDesc.round_f16) -- visible when the tile is not float16 itself: int8 127 + half 0.99 is half 128.  The result
 // (and a replaced cell's update) is stored with the astype rules of sp_store_vec.  V consecutive elements of the
 // innermost box dimension per thread (contiguous in both tile and update).
 template <typename T, int V>
@@ -369,11 +378,24 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_update_kernel(void* __restrict__ 
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) res[v] = m[v] ? sp_apply_reducer<T>(u.reducer, old[v], upd[v]) : upd[v];
+    if constexpr (sp_is_same<T, float>::value) {
+      if (u.round_f16) {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+          if (m[v]) res[v] = sp_round_f16<T>(res[v]);
+      }
+    }
     if constexpr (sp_is_integral<T>::value) {
       // bool tile: NumPy reduced in the update's dtype (True + uint8 255 is 0 there, so False)
-      if (u.dst_dtype == SP_BOOL && (u.src_dtype == SP_U8 || u.src_dtype == SP_I32)) {
+      if (u.dst_dtype == SP_BOOL) {
+        const size_t w = sp_dtype_size(u.src_dtype);
+        const bool is_signed = u.src_dtype == SP_I8 || u.src_dtype == SP_I16 || u.src_dtype == SP_I32;
+        if (u.src_dtype != SP_BOOL && w > 0 && w < 8) {
+          const int sh = 64 - 8 * (int)w;
 #pragma unroll
-        for (int v = 0; v < V; ++v) res[v] = u.src_dtype == SP_U8 ? (T)(uint8_t)res[v] : (T)(int32_t)res[v];
+          for (int v = 0; v < V; ++v)
+            res[v] = is_signed ? (T)((int64_t)((uint64_t)res[v] << sh) >> sh) : (T)(((uint64_t)res[v] << sh) >> sh);
+        }
       }
     }
     sp_store_vec<T, V>(dst, u.dst_dtype, off, res);
@@ -384,15 +406,23 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_update_kernel(void* __restrict__ 
   }
 }
 
-// the type NumPy's reducer(old, update) computes in (tile.pyx:263-279: reduce, then cast to the tile's dtype):
-// float64 with a float64 operand or a float32 one next to int32 / int64; float32 for float32 next to float32, uint8 or
-// bool; int64 (standing in for the integer promotion) for two integer / bool operands
+// the type NumPy's reducer(old, update) computes in (tile.pyx:263-279: reduce, then cast to the tile's dtype), i.e.
+// np.result_type of the two: int64 (standing in for the integer promotion) for two integer / bool operands;
+// otherwise the widest float named by either operand -- a float operand names itself, an integer one the smallest
+// float that holds it (bool, int8, uint8: float16; int16, uint16: float32; int32, uint32, int64: float64).
+// Returns SP_F16 for "float16": float arithmetic, result rounded to half (UpdDesc.round_f16).
+static int sp_float_level(int32_t dt) {
+  switch (dt) {
+    case SP_F16: case SP_BOOL: case SP_U8: case SP_I8: return 0;
+    case SP_F32: case SP_I16: case SP_U16: return 1;
+    default: return 2;
+  }
+}
+static bool sp_is_float_dtype(int32_t dt) { return dt == SP_F16 || dt == SP_F32 || dt == SP_F64; }
 static int sp_merge_class(int32_t dst, int32_t src) {
-  const bool wide_int_d = dst == SP_I32 || dst == SP_I64, wide_int_s = src == SP_I32 || src == SP_I64;
-  if (dst == SP_F64 || src == SP_F64) return SP_F64;
-  if (dst == SP_F32) return wide_int_s ? SP_F64 : SP_F32;
-  if (src == SP_F32) return wide_int_d ? SP_F64 : SP_F32;
-  return SP_I64;
+  if (!sp_is_float_dtype(dst) && !sp_is_float_dtype(src)) return SP_I64;
+  const int a = sp_float_level(dst), b = sp_float_level(src), level = a > b ? a : b;
+  return level == 0 ? SP_F16 : (level == 1 ? SP_F32 : SP_F64);
 }
 
 template <typename T>
@@ -454,7 +484,10 @@ extern "C" int sp_update(void* d_dst, int32_t dst_dtype, const int64_t* dst_shap
   }
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  switch (sp_merge_class(dst_dtype, src_dtype)) {
+  const int cls = sp_merge_class(dst_dtype, src_dtype);
+  u.round_f16 = cls == SP_F16 ? 1 : 0;
+  switch (cls) {
+    case SP_F16:
     case SP_F32: return sp_update_launch<float>(d_dst, d_src, d_mask, u, n, st);
     case SP_F64: return sp_update_launch<double>(d_dst, d_src, d_mask, u, n, st);
     default: return sp_update_launch<int64_t>(d_dst, d_src, d_mask, u, n, st);
@@ -563,17 +596,23 @@ extern "C" int sp_gather_rows(const void* d_src, int64_t src_row_stride_bytes, i
   if (n_idx < 0 || row_bytes < 0 || n_src_rows < 0 || src_row_stride_bytes < row_bytes) SP_FAIL("sp_gather_rows: bad sizes");
   if (n_idx == 0 || row_bytes == 0) return 0;
   if (!d_src || !d_idx || !d_dst) SP_FAIL("sp_gather_rows: NULL pointer");
-  if (row_bytes % 4 || src_row_stride_bytes % 4) SP_FAIL("sp_gather_rows: rows must be a multiple of 4 bytes");
+  if (row_bytes % 2 || src_row_stride_bytes % 2) SP_FAIL("sp_gather_rows: rows must be a multiple of 2 bytes");
   hipStream_t st = (hipStream_t)stream;
   const bool wide = row_bytes % 16 == 0 && src_row_stride_bytes % 16 == 0 && ((uintptr_t)d_src % 16) == 0 &&
                     ((uintptr_t)d_dst % 16) == 0;
-  const int64_t words = wide ? row_bytes / 16 : row_bytes / 4;
+  const bool half_words = !wide && (row_bytes % 4 || src_row_stride_bytes % 4);   // rows of 2-byte elements, odd length
+  if (half_words && (((uintptr_t)d_src | (uintptr_t)d_dst) & 1))
+    SP_FAIL("sp_gather_rows: rows of %lld bytes need 2-byte aligned pointers", (long long)row_bytes);
+  const int64_t words = wide ? row_bytes / 16 : (half_words ? row_bytes / 2 : row_bytes / 4);
   int64_t blocks = (n_idx * words + 255) / 256;
   const int64_t cap = (int64_t)SP_CUS * SP_BLOCKS_PER_CU * 4;
   if (blocks > cap) blocks = cap;
   if (wide)
     hipLaunchKernelGGL((sp_gather_rows_kernel<float4>), dim3((unsigned)blocks), dim3(256), 0, st, (const float4*)d_src,
                        src_row_stride_bytes / 16, d_idx, n_idx, n_src_rows, words, (float4*)d_dst);
+  else if (half_words)
+    hipLaunchKernelGGL((sp_gather_rows_kernel<uint16_t>), dim3((unsigned)blocks), dim3(256), 0, st, (const uint16_t*)d_src,
+                       src_row_stride_bytes / 2, d_idx, n_idx, n_src_rows, words, (uint16_t*)d_dst);
   else
     hipLaunchKernelGGL((sp_gather_rows_kernel<uint32_t>), dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t*)d_src,
                        src_row_stride_bytes / 4, d_idx, n_idx, n_src_rows, words, (uint32_t*)d_dst);

@@ -470,7 +470,12 @@ def trace(op, args, ex):
 
 
 # -------------------------------------------------------------------- emission
-_NORMALISE = {np.dtype(np.float32): 'TO_F32', np.dtype(np.int32): 'TO_I32', np.dtype(np.uint8): 'TO_U8'}
+# dtype -> (narrowing operator, width selector in the instruction's c field: include/spartan_hip.h) keeping a value
+# inside a NumPy dtype narrower than the arithmetic class; int64 / float64 are the classes themselves
+_NORMALISE = {np.dtype(np.float32): ('TO_F32', 0), np.dtype(np.float16): ('TO_F32', 1),
+              np.dtype(np.int32): ('TO_I32', 0), np.dtype(np.int8): ('TO_I32', 1), np.dtype(np.int16): ('TO_I32', 2),
+              np.dtype(np.uint8): ('TO_U8', 0), np.dtype(np.uint16): ('TO_U8', 1), np.dtype(np.uint32): ('TO_U8', 2),
+              np.dtype(np.int64): ('TO_I64', 0)}
 # operator -> (name when the RIGHT operand is the constant, name when the LEFT one is): reg[b] (op) consts[a]
 _WITH_CONST = {'ADD': ('ADDC', 'ADDC'), 'SUB': ('SUBC', 'RSUBC'), 'MUL': ('MULC', 'MULC'), 'DIV': ('DIVC', 'RDIVC'),
                'MAX': ('MAXC', 'MAXC'), 'MIN': ('MINC', 'MINC')}
@@ -680,20 +685,23 @@ class Emitter(object):
       src_dt, dst_dt = v.args[0].dtype, v.dtype
       op = None
       if dst_dt == np.bool_:
-        op = None if src_dt == np.bool_ else 'TO_BOOL'
+        op = None if src_dt == np.bool_ else ('TO_BOOL', 0)
       elif dst_dt.kind in 'iu':
-        name = {1: 'TO_U8', 4: 'TO_I32', 8: 'TO_I64'}[dst_dt.itemsize]
+        if dst_dt not in _NORMALISE:
+          _hip.sp_dtype(dst_dt)                       # (uint64: refused with the list of supported types)
         if src_dt.kind == 'f':
-          op = name                                   # truncate toward zero
-        elif src_dt.kind in 'iu' and src_dt.itemsize > dst_dt.itemsize:
-          op = name                                   # wrap
+          op = _NORMALISE[dst_dt]                     # truncate toward zero
+        elif src_dt.kind in 'iu' and not np.can_cast(src_dt, dst_dt, 'safe'):
+          op = _NORMALISE[dst_dt]                     # wrap
       elif dst_dt == np.float32:
-        op = 'TO_F32' if self.cls != _hip.SP_F32 else None
+        op = _NORMALISE[dst_dt] if self.cls != _hip.SP_F32 else None
+      elif dst_dt == np.float16:
+        op = None if np.can_cast(src_dt, dst_dt, 'safe') else _NORMALISE[dst_dt]   # round to half, once
       if op is None:
         return r
       self.release(r)
       dst = self.alloc()                      # (r itself when this was its last use)
-      p.emit(op, dst, r)
+      p.emit(op[0], dst, r, 0, op[1])
       return dst
     # an operator with ONE constant operand is one instruction (`x + c` -> ADDC): no CONST into a register first
     with_const = None
@@ -722,13 +730,12 @@ class Emitter(object):
       p.emit(v.op, dst, regs[0])
     else:
       p.emit(v.op, dst, regs[0], regs[1])
-    # keep the value inside its NumPy dtype when the class is wider
-    if v.op not in _NO_NORMALISE_OPS and v.dtype in _NORMALISE and class_of(v.dtype) != self.cls:
-      p.emit(_NORMALISE[v.dtype], dst, dst)
-    elif v.op not in _NO_NORMALISE_OPS and v.dtype == np.int32 and self.cls == _hip.SP_I64:
-      p.emit('TO_I32', dst, dst)
-    elif v.op not in _NO_NORMALISE_OPS and v.dtype == np.uint8:
-      p.emit('TO_U8', dst, dst)
+    # keep the value inside its NumPy dtype when the class is wider: NumPy rounds and wraps after every node
+    # (int8 * int8 wraps at 8 bits before the next operator, float16 * float16 is rounded to half)
+    norm = _NORMALISE.get(v.dtype)
+    if v.op not in _NO_NORMALISE_OPS and norm is not None and norm[0] != 'TO_I64' and \
+        not (v.dtype == np.float32 and self.cls == _hip.SP_F32):
+      p.emit(norm[0], dst, dst, 0, norm[1])
     return dst
 
   def finish(self, root, out_dtype):

@@ -20,7 +20,7 @@ class ProgramTooLarge(Exception):
 def class_of(dtype):
   """Arithmetic class (sp_program.cls) able to represent `dtype` exactly."""
   dtype = np.dtype(dtype)
-  if dtype == np.float32:
+  if dtype == np.float32 or dtype == np.float16:    # (every half is a float: exact)
     return SP_F32
   if dtype == np.float64:
     return SP_F64
