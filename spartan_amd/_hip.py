@@ -66,6 +66,14 @@ def refuse_narrow(dt, what):
                     'bool uint8 where the kernel takes them); convert with astype first' % (dt, what))
 
 
+def refuse_not_float(dt, what):
+  """The loud refusal of a kernel that exists in float32 and float64 only (the dense factorisation kernels)."""
+  dt = np.dtype(dt)
+  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+    raise TypeError('dtype %s is not supported by %s of the HIP tile backend (supported: float32 float64); convert '
+                    'with astype first' % (dt, what))
+
+
 class sp_instr(C.Structure):
   _fields_ = [('op', C.c_uint8), ('dst', C.c_uint8), ('a', C.c_uint8), ('b', C.c_uint8),
               ('c', C.c_uint8), ('pad0', C.c_uint8), ('pad1', C.c_uint8), ('pad2', C.c_uint8)]
@@ -260,12 +268,12 @@ def source_sha():
 
 # every symbol include/spartan_hip_extras.h declares (libspartan_hip_extras.so: `make extras`)
 EXTRAS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), 'libspartan_hip_extras.so')
-EXPORTS_EXTRAS = ['sp_sort_rows_workspace_bytes', 'sp_sort_rows']
+EXPORTS_EXTRAS = ['sp_sort_rows_workspace_bytes', 'sp_sort_rows', 'sp_potrf_workspace_bytes', 'sp_potrf', 'sp_trsm_rlt']
 _extras = None
 
 
 def extras():
-  """The library of kernels outside the tile path (sort); raises if it has not been built."""
+  """The library of kernels outside the tile path (sort, potrf / trsm_rlt); raises if it has not been built."""
   global _extras
   if _extras is None:
     lib()
@@ -277,6 +285,10 @@ def extras():
     x.sp_sort_rows_workspace_bytes.argtypes = [i32, i64, i64]
     x.sp_sort_rows_workspace_bytes.restype = sz
     x.sp_sort_rows.argtypes = [vp, i32, i64, i64, vp, vp, vp, sz, vp]
+    x.sp_potrf_workspace_bytes.argtypes = [i32, i64]
+    x.sp_potrf_workspace_bytes.restype = sz
+    x.sp_potrf.argtypes = [i32, vp, i64, i64, vp, sz, vp, vp]
+    x.sp_trsm_rlt.argtypes = [i32, vp, i64, i64, vp, i64, i64, vp]
     _extras = x
   return _extras
 

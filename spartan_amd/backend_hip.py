@@ -1147,6 +1147,44 @@ class HipBackend(object):
     out = (idx if indices else vals).reshape(outer, inner, n)
     return self.contiguous(out.movedim(2, 1)).reshape(shape)
 
+  def potrf(self, t):
+    """scipy.linalg.lapack.potrf(t, lower=1, clean=1)[0] as a NEW tensor: the Cholesky factor L of the symmetric
+    positive definite fp32 / fp64 matrix `t` (its lower triangle is read), zero above the diagonal (sp_potrf;
+    examples/cholesky.py:9-13).  numpy.linalg.LinAlgError, with LAPACK's words, if a leading minor is not positive
+    definite -- learnt from one 4-byte copy to the host, the only point at which this call waits for the device."""
+    t = self._as_device(t)
+    dt = self.dtype_of(t)
+    _hip.refuse_not_float(dt, 'potrf')
+    if t.dim() != 2 or t.shape[0] != t.shape[1]:
+      raise ValueError('potrf: expected a square matrix, got shape %s' % (tuple(t.shape),))
+    out = self.copy(t)           # (a strided view becomes contiguous here; the input is never written)
+    if t.shape[0] == 0:
+      return out
+    info = self.empty((1,), np.int32)
+    self.launches += 1
+    kernels.potrf(out, info)
+    order = int(info.numpy()[0])
+    if order:
+      raise np.linalg.LinAlgError('%d-th leading minor of the array is not positive definite' % order)
+    return out
+
+  def trsm_rlt(self, b, l):
+    """x with x . l^T = b as a NEW tensor: `l` [n, n] lower triangular, `b` [m, n] (sp_trsm_rlt) -- scipy's
+    dtrtrs(l, b.T, lower=1)[0].T (examples/cholesky.py:16-20), b . inv(l.T) without the inverse (ssvd/qr.py:40-43)."""
+    b, l = self._as_device(b), self._as_device(l)
+    for t in (b, l):
+      _hip.refuse_not_float(self.dtype_of(t), 'trsm_rlt')
+    if self.dtype_of(b) != self.dtype_of(l):
+      raise TypeError('trsm_rlt: operands of two dtypes (%s, %s); convert with astype first'
+                      % (self.dtype_of(b), self.dtype_of(l)))
+    if b.dim() != 2 or l.dim() != 2 or l.shape[0] != l.shape[1] or b.shape[1] != l.shape[0]:
+      raise ValueError('trsm_rlt: shapes %s and %s do not fit' % (tuple(b.shape), tuple(l.shape)))
+    out = self.copy(b)
+    if out.numel():
+      self.launches += 1
+      kernels.trsm_rlt(out, self.contiguous(l))
+    return out
+
   def convolve(self, image, filters):
     """stencil.py:29-45 as a GEMM: P[(n, x, y), (c, i, j)] = image[n, c, x+i, y+j] (0 beyond the edge) by one strided
     box copy per (c, i, j); P . filters[(c, i, j), f] on the MFMA GEMM; back to [n, f, x, y]."""

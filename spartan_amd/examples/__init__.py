@@ -1,3 +1,6 @@
 """Workload drivers for the two application configs of BASELINE.json: `lreg` (configs[4], least squares
 by gradient steps) and `sklearn.cluster.KMeans` (configs[3]); `logreg` is the logistic member of lreg's SGD family.
-They are thin driver loops over the expression API; every per-tile body runs in HIP kernels through the backend."""
+They are thin driver loops over the expression API; every per-tile body runs in HIP kernels through the backend.
+`cholesky` (the blocked factorisation over map2's region join) and `ssvd.qr` (the thin Cholesky-QR) stand on the dense
+factorisation kernels outside the tile path (sp_potrf / sp_trsm_rlt); like `sort` they are imported on first use, not
+with the package."""

@@ -309,6 +309,41 @@ def sort_rows(src, values=True, indices=False):
   return vals, idx
 
 
+def potrf(a, info):
+  """In place: the lower triangle of the square fp32 / fp64 matrix `a` (a view with inner stride 1 will do) becomes
+  its Cholesky factor L, the strict upper triangle zero (sp_potrf); `info`, a device int32, receives 0 or the order
+  of the first leading minor that is not positive definite.  Nothing waits for the device."""
+  _require_device(a, info)
+  dt = np_dtype_of(a)
+  _hip.refuse_not_float(dt, 'potrf')
+  assert a.dim() == 2 and a.shape[0] == a.shape[1] and np_dtype_of(info) == np.int32
+  n = int(a.shape[0])
+  assert n <= 1 or a.stride(1) == 1
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  ws = _ws.get(lib.sp_potrf_workspace_bytes(code, n), a.device)
+  check(lib.sp_potrf(code, C.c_void_p(a.data_ptr()), _ld(a), n, C.c_void_p(ws.data_ptr()), ws.numel(),
+                     C.c_void_p(info.data_ptr()), _stream()))
+  return a
+
+
+def trsm_rlt(b, l):
+  """In place: b <- x with x . l^T = b, `l` square lower triangular (its upper triangle is not read), `b` [m, n]; both
+  fp32 or both fp64, views with inner stride 1 (sp_trsm_rlt)."""
+  _require_device(b, l)
+  dt = np_dtype_of(b)
+  _hip.refuse_not_float(dt, 'trsm_rlt')
+  _hip.refuse_not_float(np_dtype_of(l), 'trsm_rlt')
+  assert dt == np_dtype_of(l) and b.dim() == 2 and l.dim() == 2
+  m, n = (int(v) for v in b.shape)
+  assert tuple(l.shape) == (n, n), (b.shape, l.shape)
+  assert n <= 1 or (b.stride(1) == 1 and l.stride(1) == 1)
+  if m and n:
+    check(_hip.extras().sp_trsm_rlt(_hip.sp_dtype(dt), C.c_void_p(l.data_ptr()), _ld(l), n, C.c_void_p(b.data_ptr()),
+                                    _ld(b), m, _stream()))
+  return b
+
+
 def gather_rows(src, idx):
   """src[idx] along axis 0 for a contiguous tensor and a device int64 index vector (filter.py:50-75)."""
   _require_device(src, idx)
