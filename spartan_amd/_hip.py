@@ -67,7 +67,8 @@ def refuse_narrow(dt, what):
 
 
 def refuse_not_float(dt, what):
-  """The loud refusal of a kernel that exists in float32 and float64 only (the dense factorisation kernels)."""
+  """The loud refusal of a kernel that exists in float32 and float64 only (the dense factorisation and eigenvalue
+  kernels)."""
   dt = np.dtype(dt)
   if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
     raise TypeError('dtype %s is not supported by %s of the HIP tile backend (supported: float32 float64); convert '
@@ -269,11 +270,13 @@ def source_sha():
 # every symbol include/spartan_hip_extras.h declares (libspartan_hip_extras.so: `make extras`)
 EXTRAS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), 'libspartan_hip_extras.so')
 EXPORTS_EXTRAS = ['sp_sort_rows_workspace_bytes', 'sp_sort_rows', 'sp_potrf_workspace_bytes', 'sp_potrf', 'sp_trsm_rlt']
+# every symbol include/spartan_hip_eig.h declares (the same library)
+EXPORTS_EIG = ['sp_syevj_workspace_bytes', 'sp_syevj']
 _extras = None
 
 
 def extras():
-  """The library of kernels outside the tile path (sort, potrf / trsm_rlt); raises if it has not been built."""
+  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj); raises if it has not been built."""
   global _extras
   if _extras is None:
     lib()
@@ -289,6 +292,9 @@ def extras():
     x.sp_potrf_workspace_bytes.restype = sz
     x.sp_potrf.argtypes = [i32, vp, i64, i64, vp, sz, vp, vp]
     x.sp_trsm_rlt.argtypes = [i32, vp, i64, i64, vp, i64, i64, vp]
+    x.sp_syevj_workspace_bytes.argtypes = [i32, i64]
+    x.sp_syevj_workspace_bytes.restype = sz
+    x.sp_syevj.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, sz, vp, C.POINTER(C.c_int32), vp]
     _extras = x
   return _extras
 

@@ -1185,6 +1185,31 @@ class HipBackend(object):
       kernels.trsm_rlt(out, self.contiguous(l))
     return out
 
+  def syev(self, t):
+    """(w, V) as NEW tensors: the eigenvalues of the symmetric fp32 / fp64 matrix `t` in ascending order and the
+    eigenvectors as the columns of V, t . V = V . diag(w) (sp_syevj, two-sided Jacobi; LAPACK's syevd(t, lower=1): the
+    lower triangle of `t` is read, `t` is not written).  numpy.linalg.LinAlgError if 64 sweeps do not converge (a NaN
+    in `t`).  Waits for the device once per sweep (one word) and once for info; self.syev_sweeps holds the number of
+    sweeps of the last call."""
+    t = self._as_device(t)
+    dt = self.dtype_of(t)
+    _hip.refuse_not_float(dt, 'syev')
+    if t.dim() != 2 or t.shape[0] != t.shape[1]:
+      raise ValueError('syev: expected a square matrix, got shape %s' % (tuple(t.shape),))
+    n = int(t.shape[0])
+    w, v = self.empty((n,), dt), self.empty((n, n), dt)
+    self.syev_sweeps = 0
+    if n == 0:
+      return w, v
+    if n > 1 and t.stride(1) != 1:
+      t = self.contiguous(t)
+    info = self.empty((1,), np.int32)
+    self.launches += 1
+    self.syev_sweeps = kernels.syevj(t, w, v, info)
+    if int(info.numpy()[0]):
+      raise np.linalg.LinAlgError('Eigenvalues did not converge')
+    return w, v
+
   def convolve(self, image, filters):
     """stencil.py:29-45 as a GEMM: P[(n, x, y), (c, i, j)] = image[n, c, x+i, y+j] (0 beyond the edge) by one strided
     box copy per (c, i, j); P . filters[(c, i, j), f] on the MFMA GEMM; back to [n, f, x, y]."""

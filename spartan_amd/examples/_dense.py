@@ -1,6 +1,6 @@
-"""The two dense tile bodies the Cholesky drivers share: backend.potrf / backend.trsm_rlt where the backend has them
-(HipBackend: sp_potrf / sp_trsm_rlt), LAPACK on host arrays otherwise, as in the reference -- which keeps the drivers
-runnable on a backend of plain NumPy tiles."""
+"""The dense tile bodies the Cholesky, QR and SVD drivers share: backend.potrf / backend.trsm_rlt / backend.syev where
+the backend has them (HipBackend: sp_potrf / sp_trsm_rlt / sp_syevj), LAPACK on host arrays otherwise, as in the
+reference -- which keeps the drivers runnable on a backend of plain NumPy tiles."""
 import numpy as np
 
 from .. import context
@@ -46,3 +46,21 @@ def trsm_rlt(b, low):
   if info:
     raise np.linalg.LinAlgError('trsm_rlt: the triangular matrix is singular (zero at position %d of its diagonal)' % info)
   return np.ascontiguousarray(xt.T)
+
+
+def syev(t):
+  """(w, V): the eigenvalues of the symmetric tile `t` (its lower triangle is read) in ascending order and the
+  eigenvectors as the columns of V."""
+  be = context.get().backend
+  fn = getattr(be, 'syev', None)
+  if fn is not None:
+    return fn(t)
+  t = np.asarray(be.to_numpy(t))
+  if t.ndim != 2 or t.shape[0] != t.shape[1]:
+    raise ValueError('syev: expected a square matrix, got shape %s' % (t.shape,))
+  if t.shape[0] == 0:
+    return np.empty((0,), t.dtype), t.copy()
+  w, v, info = _lapack('syevd', t)(t, lower=1)
+  if info:
+    raise np.linalg.LinAlgError('Eigenvalues did not converge')
+  return w, np.ascontiguousarray(v)

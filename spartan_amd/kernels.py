@@ -344,6 +344,28 @@ def trsm_rlt(b, l):
   return b
 
 
+def syevj(a, w, v, info):
+  """Eigenvalues (ascending, into the vector `w`) and eigenvectors (the columns of `v`, same order) of the symmetric
+  fp32 / fp64 matrix `a`, whose lower triangle is read and which is NOT written (sp_syevj: cyclic two-sided Jacobi);
+  `a` and `v` may be views with inner stride 1.  `info`, a device int32, receives 0, or 1 if 64 sweeps did not
+  converge.  Returns the number of sweeps.  The call waits for the device once per sweep (a word that says whether
+  the off-diagonal norm is below n u ||a||_F) and for nothing else."""
+  _require_device(a, w, v, info)
+  dt = np_dtype_of(a)
+  _hip.refuse_not_float(dt, 'syevj')
+  assert a.dim() == 2 and a.shape[0] == a.shape[1] and np_dtype_of(info) == np.int32
+  n = int(a.shape[0])
+  assert np_dtype_of(w) == dt and np_dtype_of(v) == dt and tuple(w.shape) == (n,) and tuple(v.shape) == (n, n)
+  assert n <= 1 or (a.stride(1) == 1 and v.stride(1) == 1 and w.stride(0) == 1)
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  ws = _ws.get(lib.sp_syevj_workspace_bytes(code, n), a.device)
+  sweeps = C.c_int32(0)
+  check(lib.sp_syevj(code, C.c_void_p(a.data_ptr()), _ld(a), n, C.c_void_p(w.data_ptr()), C.c_void_p(v.data_ptr()), _ld(v),
+                     C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(info.data_ptr()), C.byref(sweeps), _stream()))
+  return int(sweeps.value)
+
+
 def gather_rows(src, idx):
   """src[idx] along axis 0 for a contiguous tensor and a device int64 index vector (filter.py:50-75)."""
   _require_device(src, idx)

@@ -1,7 +1,8 @@
 """Times sp_potrf and sp_trsm_rlt with HIP events, next to the host route a driver would otherwise take for the same
-tile (device-to-host copy, SciPy's LAPACK, copy back) and to the GEMM rate of the same dtype.
+tile (device-to-host copy, SciPy's LAPACK, copy back) and to the GEMM rate of the same dtype; and sp_syevj (wall
+time: the call waits for the device once per sweep) next to its host route (copy, LAPACK's syevd, two copies back).
 
-  python tools/bench_linalg.py [--orders 2048,4096,8192] [--reps 3] [--out profiles/linalg_rates.json]
+  python tools/bench_linalg.py [--orders 2048,4096,8192] [--syev 64,256,1024] [--reps 3] [--out profiles/linalg_rates.json]
 
 Every figure is the median of `reps` runs after one warm-up run; prints one JSON line per case."""
 import argparse
@@ -61,6 +62,7 @@ def main():
   ap.add_argument('--dtypes', default='float32,float64')
   ap.add_argument('--reps', type=int, default=3)
   ap.add_argument('--trsm', default='65536x256')
+  ap.add_argument('--syev', default='64,256,1024')
   ap.add_argument('--out', default=None)
   args = ap.parse_args()
   from scipy.linalg import lapack
@@ -129,6 +131,33 @@ def main():
       rows.append(dict(kernel='trsm_rlt', dtype=name, m=m, n=n, device_ms=round(dev_ms, 3), tflops=round(rate, 3),
                        fraction_of_gemm=round(rate / gemm_rate, 4), gemm_tflops=round(gemm_rate, 2),
                        host_route_ms=round(host_ms, 3)))
+      print(json.dumps(rows[-1]), flush=True)
+    for n in (int(v) for v in args.syev.split(',') if v):
+      g = np.random.RandomState(20150708).randn(n, n)
+      host = ((g + g.T) / 2).astype(dtype)
+      src = be.from_numpy(host)
+      w, v, info = be.empty((n,), dtype), be.empty((n, n), dtype), be.zeros((1,), np.int32)
+      sweeps = []
+
+      def device():
+        sweeps.append(kernels.syevj(src, w, v, info))
+        D.synchronize()
+
+      dev_ms = _wall(device, args.reps)
+      assert int(info.numpy()[0]) == 0
+      syevd = lapack.get_lapack_funcs(('syevd',), (host,))[0]
+
+      def host_route():
+        h = src.numpy()
+        wh, vh, bad = syevd(h, lower=1)
+        be.from_numpy(wh)
+        be.from_numpy(np.ascontiguousarray(vh))
+        D.synchronize()
+
+      host_ms = _wall(host_route, args.reps)
+      lapack_ms = _wall(lambda: syevd(host, lower=1), args.reps)
+      rows.append(dict(kernel='syev', dtype=name, n=n, sweeps=sweeps[-1], device_wall_ms=round(dev_ms, 3),
+                       host_route_ms=round(host_ms, 3), lapack_only_ms=round(lapack_ms, 3)))
       print(json.dumps(rows[-1]), flush=True)
   sp.shutdown()
   if args.out:
