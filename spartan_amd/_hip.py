@@ -272,11 +272,15 @@ EXTRAS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), 'libspartan_hip_extras
 EXPORTS_EXTRAS = ['sp_sort_rows_workspace_bytes', 'sp_sort_rows', 'sp_potrf_workspace_bytes', 'sp_potrf', 'sp_trsm_rlt']
 # every symbol include/spartan_hip_eig.h declares (the same library)
 EXPORTS_EIG = ['sp_syevj_workspace_bytes', 'sp_syevj']
+# every symbol include/spartan_hip_knn.h declares (the same library), and its SP_KNN_MAX_K
+EXPORTS_KNN = ['sp_knn_workspace_bytes', 'sp_knn', 'sp_knn_merge']
+KNN_MAX_K = 128
 _extras = None
 
 
 def extras():
-  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj); raises if it has not been built."""
+  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn); raises if it has not been
+  built."""
   global _extras
   if _extras is None:
     lib()
@@ -295,6 +299,10 @@ def extras():
     x.sp_syevj_workspace_bytes.argtypes = [i32, i64]
     x.sp_syevj_workspace_bytes.restype = sz
     x.sp_syevj.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, sz, vp, C.POINTER(C.c_int32), vp]
+    x.sp_knn_workspace_bytes.argtypes = [i32, i64, i64, i64, i32, i32]
+    x.sp_knn_workspace_bytes.restype = sz
+    x.sp_knn.argtypes = [i32, vp, i64, i64, vp, i64, i64, i64, i32, i64, i32, vp, vp, vp, sz, vp]
+    x.sp_knn_merge.argtypes = [i32, vp, vp, i64, i64, i64, i32, vp, vp, vp]
     _extras = x
   return _extras
 

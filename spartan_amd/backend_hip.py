@@ -1210,6 +1210,64 @@ class HipBackend(object):
       raise np.linalg.LinAlgError('Eigenvalues did not converge')
     return w, v
 
+  def _knn_rows(self, t):
+    """A 2-D operand of the knn kernels as a view with inner stride 1: the tensor itself where it is one (a row view
+    of a wider array included), a contiguous copy otherwise."""
+    rows_apart = t.shape[0] <= 1 or t.stride(0) >= t.shape[1]
+    return t if (t.shape[1] <= 1 or t.stride(1) == 1) and rows_apart else self.contiguous(t)
+
+  def knn(self, queries, points, k, index_offset=0, splits=0):
+    """(dist2, idx) as NEW tensors [nq, k]: for every row of `queries` [nq, d] the k rows of `points` [np, d] at the
+    smallest squared Euclidean distance sum_j (q_j - x_j)^2 (computed in that form, in the operands' precision),
+    ascending by (distance, index); idx (int64) = index_offset + row of `points`; +inf / -1 in the trailing slots when
+    np < k (sp_knn: distance and selection in one pass, nothing of size nq x np is written).  Both operands fp32 or
+    both fp64; 1 <= k <= 128.  splits: into how many ranges the points are cut (0: the library chooses); the result
+    does not depend on it, bit for bit."""
+    queries, points = self._as_device(queries), self._as_device(points)
+    dt = self.dtype_of(queries)
+    for t in (queries, points):
+      _hip.refuse_not_float(self.dtype_of(t), 'knn')
+    if dt != self.dtype_of(points):
+      raise TypeError('knn: operands of two dtypes (%s, %s); convert with astype first' % (dt, self.dtype_of(points)))
+    if queries.dim() != 2 or points.dim() != 2 or queries.shape[1] != points.shape[1]:
+      raise ValueError('knn: shapes %s and %s do not fit' % (tuple(queries.shape), tuple(points.shape)))
+    k = int(k)
+    if not 1 <= k <= _hip.KNN_MAX_K:
+      raise ValueError('knn: k = %d is outside 1 .. %d' % (k, _hip.KNN_MAX_K))
+    if int(splits) < 0:
+      raise ValueError('knn: splits = %d is negative' % int(splits))
+    nq = int(queries.shape[0])
+    dist2, idx = self.empty((nq, k), dt), self.empty((nq, k), np.int64)
+    if nq:
+      self.launches += 1
+      kernels.knn(self._knn_rows(queries), self._knn_rows(points), k, dist2, idx, index_offset, splits)
+    return dist2, idx
+
+  def knn_merge(self, cand_dist2, cand_idx, k):
+    """(dist2, idx) as NEW tensors [nq, k]: per row the k smallest by (distance, index) of the m candidates
+    (cand_dist2 fp32 / fp64, cand_idx int64, both [nq, m]); candidates with a negative index are padding, and so are
+    the trailing slots of the result (+inf / -1) when fewer than k are left (sp_knn_merge)."""
+    cand_dist2, cand_idx = self._as_device(cand_dist2), self._as_device(cand_idx)
+    dt = self.dtype_of(cand_dist2)
+    _hip.refuse_not_float(dt, 'knn_merge')
+    if self.dtype_of(cand_idx) != np.int64:
+      raise TypeError('knn_merge: candidate indices of dtype %s (int64 expected); convert with astype first'
+                      % (self.dtype_of(cand_idx),))
+    if cand_dist2.dim() != 2 or tuple(cand_dist2.shape) != tuple(cand_idx.shape):
+      raise ValueError('knn_merge: shapes %s and %s do not fit' % (tuple(cand_dist2.shape), tuple(cand_idx.shape)))
+    k = int(k)
+    if not 1 <= k <= _hip.KNN_MAX_K:
+      raise ValueError('knn_merge: k = %d is outside 1 .. %d' % (k, _hip.KNN_MAX_K))
+    nq = int(cand_dist2.shape[0])
+    dist2, idx = self.empty((nq, k), dt), self.empty((nq, k), np.int64)
+    if nq:
+      cand_dist2, cand_idx = self._knn_rows(cand_dist2), self._knn_rows(cand_idx)
+      if nq > 1 and cand_dist2.stride(0) != cand_idx.stride(0):      # (the kernel takes one row stride for both)
+        cand_dist2, cand_idx = self.contiguous(cand_dist2), self.contiguous(cand_idx)
+      self.launches += 1
+      kernels.knn_merge(cand_dist2, cand_idx, k, dist2, idx)
+    return dist2, idx
+
   def convolve(self, image, filters):
     """stencil.py:29-45 as a GEMM: P[(n, x, y), (c, i, j)] = image[n, c, x+i, y+j] (0 beyond the edge) by one strided
     box copy per (c, i, j); P . filters[(c, i, j), f] on the MFMA GEMM; back to [n, f, x, y]."""

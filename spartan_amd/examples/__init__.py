@@ -3,5 +3,6 @@ by gradient steps) and `sklearn.cluster.KMeans` (configs[3]); `logreg` is the lo
 They are thin driver loops over the expression API; every per-tile body runs in HIP kernels through the backend.
 `cholesky` (the blocked factorisation over map2's region join) and `ssvd.qr` (the thin Cholesky-QR) stand on the dense
 factorisation kernels outside the tile path (sp_potrf / sp_trsm_rlt); `ssvd.ssvd` (the stochastic SVD: qr, then the
-symmetric eigenproblem of the small B . B^T on sp_syevj) and `pca` (PCA on that SVD) complete the chain.  Like `sort`
-they are imported on first use, not with the package."""
+symmetric eigenproblem of the small B . B^T on sp_syevj) and `pca` (PCA on that SVD) complete the chain;
+`sklearn.neighbors.NearestNeighbors` searches row bands of X with sp_knn and merges their candidates with sp_knn_merge.
+Like `sort` they are imported on first use, not with the package."""

@@ -366,6 +366,50 @@ def syevj(a, w, v, info):
   return int(sweeps.value)
 
 
+def knn(q, x, k, dist2, idx, index_offset=0, splits=0):
+  """dist2[i], idx[i] <- the k rows of `x` [np, d] nearest to row i of `q` [nq, d] by squared Euclidean distance
+  (difference form), ascending by (distance, index); idx = index_offset + row of x, padded with +inf / -1 when np < k
+  (sp_knn).  q, x: both fp32 or both fp64, views with inner stride 1; dist2 (their dtype) and idx (int64): contiguous
+  [nq, k].  splits: 0 = the library chooses into how many ranges the points are cut, s >= 1 = min(s, np) ranges."""
+  _require_device(q, x, dist2, idx)
+  dt = np_dtype_of(q)
+  _hip.refuse_not_float(dt, 'knn')
+  _hip.refuse_not_float(np_dtype_of(x), 'knn')
+  assert dt == np_dtype_of(x) == np_dtype_of(dist2) and np_dtype_of(idx) == np.int64
+  assert q.dim() == 2 and x.dim() == 2 and q.shape[1] == x.shape[1], (q.shape, x.shape)
+  nq, d = (int(v) for v in q.shape)
+  n = int(x.shape[0])
+  k = int(k)
+  assert tuple(dist2.shape) == (nq, k) and tuple(idx.shape) == (nq, k) and dist2.is_contiguous() and idx.is_contiguous()
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  need = lib.sp_knn_workspace_bytes(code, nq, n, d, k, int(splits))
+  ws = _ws.get(need, q.device) if need else None
+  check(lib.sp_knn(code, C.c_void_p(q.data_ptr()), _ld(q), nq, C.c_void_p(x.data_ptr()), _ld(x), n, d, k,
+                   int(index_offset), int(splits), C.c_void_p(dist2.data_ptr()), C.c_void_p(idx.data_ptr()),
+                   C.c_void_p(ws.data_ptr() if need else 0), ws.numel() if need else 0, _stream()))
+  return dist2, idx
+
+
+def knn_merge(cand_dist2, cand_idx, k, dist2, idx):
+  """dist2[i], idx[i] <- the k smallest by (distance, index) of the m candidates of row i; candidates with a negative
+  index are padding (sp_knn_merge).  cand_dist2 (fp32 / fp64) and cand_idx (int64): [nq, m] views with inner stride 1
+  and ONE row stride; dist2, idx: contiguous [nq, k]."""
+  _require_device(cand_dist2, cand_idx, dist2, idx)
+  dt = np_dtype_of(cand_dist2)
+  _hip.refuse_not_float(dt, 'knn_merge')
+  assert np_dtype_of(cand_idx) == np.int64 and np_dtype_of(idx) == np.int64 and np_dtype_of(dist2) == dt
+  assert cand_dist2.dim() == 2 and tuple(cand_dist2.shape) == tuple(cand_idx.shape)
+  nq, m = (int(v) for v in cand_dist2.shape)
+  k = int(k)
+  assert _ld(cand_dist2) == _ld(cand_idx), (cand_dist2.stride(), cand_idx.stride())
+  assert tuple(dist2.shape) == (nq, k) and tuple(idx.shape) == (nq, k) and dist2.is_contiguous() and idx.is_contiguous()
+  check(_hip.extras().sp_knn_merge(_hip.sp_dtype(dt), C.c_void_p(cand_dist2.data_ptr()), C.c_void_p(cand_idx.data_ptr()),
+                                   _ld(cand_dist2), nq, m, k, C.c_void_p(dist2.data_ptr()), C.c_void_p(idx.data_ptr()),
+                                   _stream()))
+  return dist2, idx
+
+
 def gather_rows(src, idx):
   """src[idx] along axis 0 for a contiguous tensor and a device int64 index vector (filter.py:50-75)."""
   _require_device(src, idx)
