@@ -1268,6 +1268,51 @@ class HipBackend(object):
       kernels.knn_merge(cand_dist2, cand_idx, k, dist2, idx)
     return dist2, idx
 
+  def apsp(self, t):
+    """The matrix of shortest-path lengths as a NEW tensor: `t` [n, n], fp32 / fp64, holds the edge lengths of a
+    directed graph (>= 0, +inf = no edge, the diagonal taken as 0; a symmetric `t` is an undirected graph); the result
+    has +inf where there is no path and 0 on the diagonal (sp_apsp: blocked Floyd-Warshall in the (min, +) semiring;
+    scipy.sparse.csgraph.shortest_path of the same weights, every path length the rounded sum of its edges).
+    ValueError if an off-diagonal entry is negative or NaN -- learnt from one 4-byte copy to the host, the only point
+    at which this call waits for the device."""
+    t = self._as_device(t)
+    dt = self.dtype_of(t)
+    _hip.refuse_not_float(dt, 'apsp')
+    if t.dim() != 2 or t.shape[0] != t.shape[1]:
+      raise ValueError('apsp: expected a square matrix, got shape %s' % (tuple(t.shape),))
+    before = self.launches
+    out = self.copy(t)           # (a strided view becomes contiguous here; the input is never written)
+    if t.shape[0] == 0:
+      return out
+    info = self.empty((1,), np.int32)
+    self.launches = before + 1   # (the call counts as one: the copy belongs to it)
+    kernels.apsp(out, info)
+    if int(info.numpy()[0]):
+      raise ValueError('apsp: negative or NaN edge length')
+    return out
+
+  def graph_from_knn(self, dist, idx):
+    """The dense undirected neighbour graph as a NEW tensor [n, n] of dist's dtype: +inf, 0 on the diagonal, and for
+    every pair (i, idx[i][e]) of the lists dist (fp32 / fp64, >= 0) and idx (int64), both [n, k], the smallest weight
+    stated for it in either direction, on both sides (sp_graph_from_knn); idx < 0 is padding.  What apsp takes."""
+    dist, idx = self._as_device(dist), self._as_device(idx)
+    dt = self.dtype_of(dist)
+    _hip.refuse_not_float(dt, 'graph_from_knn')
+    if self.dtype_of(idx) != np.int64:
+      raise TypeError('graph_from_knn: indices of dtype %s (int64 expected); convert with astype first'
+                      % (self.dtype_of(idx),))
+    if dist.dim() != 2 or tuple(dist.shape) != tuple(idx.shape):
+      raise ValueError('graph_from_knn: shapes %s and %s do not fit' % (tuple(dist.shape), tuple(idx.shape)))
+    n = int(dist.shape[0])
+    w = self.empty((n, n), dt)
+    if n:
+      dist, idx = self._knn_rows(dist), self._knn_rows(idx)
+      if n > 1 and dist.stride(0) != idx.stride(0):      # (the kernel takes one row stride for both)
+        dist, idx = self.contiguous(dist), self.contiguous(idx)
+      self.launches += 1
+      kernels.graph_from_knn(dist, idx, w)
+    return w
+
   def convolve(self, image, filters):
     """stencil.py:29-45 as a GEMM: P[(n, x, y), (c, i, j)] = image[n, c, x+i, y+j] (0 beyond the edge) by one strided
     box copy per (c, i, j); P . filters[(c, i, j), f] on the MFMA GEMM; back to [n, f, x, y]."""

@@ -4,5 +4,7 @@ They are thin driver loops over the expression API; every per-tile body runs in 
 `cholesky` (the blocked factorisation over map2's region join) and `ssvd.qr` (the thin Cholesky-QR) stand on the dense
 factorisation kernels outside the tile path (sp_potrf / sp_trsm_rlt); `ssvd.ssvd` (the stochastic SVD: qr, then the
 symmetric eigenproblem of the small B . B^T on sp_syevj) and `pca` (PCA on that SVD) complete the chain;
-`sklearn.neighbors.NearestNeighbors` searches row bands of X with sp_knn and merges their candidates with sp_knn_merge.
+`sklearn.neighbors.NearestNeighbors` searches row bands of X with sp_knn and merges their candidates with sp_knn_merge;
+`sklearn.manifold.Isomap` turns its lists into a graph (sp_graph_from_knn), takes all-pairs shortest paths (sp_apsp) and
+embeds with sp_syevj.
 Like `sort` they are imported on first use, not with the package."""

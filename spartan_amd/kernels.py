@@ -410,6 +410,41 @@ def knn_merge(cand_dist2, cand_idx, k, dist2, idx):
   return dist2, idx
 
 
+def apsp(d, info):
+  """In place: the square fp32 / fp64 matrix `d` of edge lengths (>= 0, +inf = no edge, the diagonal taken as 0; a view
+  with inner stride 1 will do) becomes the matrix of shortest-path lengths, +inf where there is no path (sp_apsp:
+  blocked Floyd-Warshall, a candidate d[i][k] + d[k][j] wins only if it is smaller).  `info`, a device int32, receives
+  0, or 1 if an off-diagonal entry is NaN or negative (`d` is then unspecified).  Nothing waits for the device."""
+  _require_device(d, info)
+  dt = np_dtype_of(d)
+  _hip.refuse_not_float(dt, 'apsp')
+  assert d.dim() == 2 and d.shape[0] == d.shape[1] and np_dtype_of(info) == np.int32
+  n = int(d.shape[0])
+  assert n <= 1 or d.stride(1) == 1
+  check(_hip.extras().sp_apsp(_hip.sp_dtype(dt), C.c_void_p(d.data_ptr()), _ld(d), n, C.c_void_p(info.data_ptr()),
+                              _stream()))
+  return d
+
+
+def graph_from_knn(dist, idx, w):
+  """w [n, n] <- the dense undirected graph of the neighbour lists dist (fp32 / fp64, >= 0) and idx (int64), both [n, k]
+  views with inner stride 1 and ONE row stride: +inf, 0 on the diagonal, and for every listed pair (i, idx[i][e]) the
+  smallest weight stated for it in either direction, on both sides; idx < 0 is padding (sp_graph_from_knn).  `w`: of
+  dist's dtype, a view with inner stride 1."""
+  _require_device(dist, idx, w)
+  dt = np_dtype_of(dist)
+  _hip.refuse_not_float(dt, 'graph_from_knn')
+  assert np_dtype_of(idx) == np.int64 and np_dtype_of(w) == dt
+  assert dist.dim() == 2 and tuple(dist.shape) == tuple(idx.shape)
+  n, k = (int(v) for v in dist.shape)
+  assert tuple(w.shape) == (n, n) and (n <= 1 or w.stride(1) == 1)
+  assert k <= 1 or (dist.stride(1) == 1 and idx.stride(1) == 1)
+  assert n <= 1 or _ld(dist) == _ld(idx), (dist.stride(), idx.stride())
+  check(_hip.extras().sp_graph_from_knn(_hip.sp_dtype(dt), C.c_void_p(dist.data_ptr()), C.c_void_p(idx.data_ptr()),
+                                        _ld(dist), n, k, C.c_void_p(w.data_ptr()), _ld(w), _stream()))
+  return w
+
+
 def gather_rows(src, idx):
   """src[idx] along axis 0 for a contiguous tensor and a device int64 index vector (filter.py:50-75)."""
   _require_device(src, idx)
