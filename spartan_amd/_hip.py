@@ -277,11 +277,14 @@ EXPORTS_KNN = ['sp_knn_workspace_bytes', 'sp_knn', 'sp_knn_merge']
 KNN_MAX_K = 128
 # every symbol include/spartan_hip_graph.h declares (the same library)
 EXPORTS_GRAPH = ['sp_apsp', 'sp_graph_from_knn']
+# every symbol include/spartan_hip_als.h declares (the same library), and its SP_ALS_MAX_F
+EXPORTS_ALS = ['sp_als_solve', 'sp_als_solve_workspace_bytes']
+SP_ALS_MAX_F = 64
 _extras = None
 
 
 def extras():
-  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp); raises if it has not been
+  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve); raises if it has not been
   built."""
   global _extras
   if _extras is None:
@@ -305,6 +308,9 @@ def extras():
     x.sp_knn_workspace_bytes.restype = sz
     x.sp_knn.argtypes = [i32, vp, i64, i64, vp, i64, i64, i64, i32, i64, i32, vp, vp, vp, sz, vp]
     x.sp_knn_merge.argtypes = [i32, vp, vp, i64, i64, i64, i32, vp, vp, vp]
+    x.sp_als_solve_workspace_bytes.argtypes = [i32, i64, i64, i32, i32]
+    x.sp_als_solve_workspace_bytes.restype = sz
+    x.sp_als_solve.argtypes = [i32, vp, i64, i64, i64, vp, i64, i32, C.c_double, C.c_double, i32, vp, i64, vp, vp, sz, vp]
     x.sp_apsp.argtypes = [i32, vp, i64, i64, vp, vp]
     x.sp_graph_from_knn.argtypes = [i32, vp, vp, i64, i64, i64, vp, i64, vp]
     _extras = x

@@ -1313,6 +1313,37 @@ class HipBackend(object):
       kernels.graph_from_knn(dist, idx, w)
     return w
 
+  def als_solve(self, ratings, factors, la, alpha, implicit=False, info=None):
+    """One half-step of alternating least squares as a NEW tensor [m, f]: row i solves A_i x = b_i, built from row i of
+    `ratings` [m, n] and `factors` [n, f] (sp_als_solve: accumulation, Cholesky and substitution fused, per row).
+      explicit   A_i = sum_{r_ij != 0} y_j y_j^T + la |S_i| I,  b_i = sum r_ij y_j;  a row without ratings is exactly 0
+      implicit   A_i = Y^T Y + sum_j alpha r_ij y_j y_j^T + la I,  b_i = sum_{r_ij > 0} (1 + alpha r_ij) y_j
+    Both operands fp32 or both fp64; 1 <= f <= 64.  `info`: a device int32 tile of one element, zeroed by the caller and
+    shared by as many calls as the caller likes; it receives 1 + the lowest failing row of the first call in which a
+    system is not positive definite (that row of the result is NaN).  Without one the outcome is not reported.  The
+    call counts as one launch when m > 0 and as none otherwise, and never waits for the device."""
+    ratings, factors = self._as_device(ratings), self._as_device(factors)
+    dt = self.dtype_of(ratings)
+    for t in (ratings, factors):
+      _hip.refuse_not_float(self.dtype_of(t), 'als_solve')
+    if dt != self.dtype_of(factors):
+      raise TypeError('als_solve: operands of two dtypes (%s, %s); convert with astype first'
+                      % (dt, self.dtype_of(factors)))
+    if ratings.dim() != 2 or factors.dim() != 2 or ratings.shape[1] != factors.shape[0]:
+      raise ValueError('als_solve: shapes %s and %s do not fit' % (tuple(ratings.shape), tuple(factors.shape)))
+    m, f = int(ratings.shape[0]), int(factors.shape[1])
+    if not 1 <= f <= _hip.SP_ALS_MAX_F:
+      raise ValueError('als_solve: f = %d is outside 1 .. %d' % (f, _hip.SP_ALS_MAX_F))
+    out = self.empty((m, f), dt)
+    if m:
+      if info is None:
+        info = self.zeros((1,), np.int32)
+      before = self.launches
+      ratings, factors = self._knn_rows(ratings), self._knn_rows(factors)
+      self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
+      kernels.als_solve(ratings, factors, la, alpha, implicit, out, info)
+    return out
+
   def convolve(self, image, filters):
     """stencil.py:29-45 as a GEMM: P[(n, x, y), (c, i, j)] = image[n, c, x+i, y+j] (0 beyond the edge) by one strided
     box copy per (c, i, j); P . filters[(c, i, j), f] on the MFMA GEMM; back to [n, f, x, y]."""

@@ -445,6 +445,39 @@ def graph_from_knn(dist, idx, w):
   return w
 
 
+def als_solve(r, y, la, alpha, implicit, x, info):
+  """x[i] <- the solution of row i's normal equations of one ALS half-step: ratings `r` [m, n], factors `y` [n, f],
+  both fp32 or both fp64, views with inner stride 1; `x` [m, f] of their dtype, a view with inner stride 1
+  (sp_als_solve; include/spartan_hip_als.h states the two modes).  `info`, a device int32 the caller has zeroed,
+  receives 1 + the lowest row whose system is not positive definite if it is still 0; that row of x is NaN.  TypeError
+  for other dtypes, ValueError for shapes that do not fit or f outside 1 .. 64.  Nothing waits for the device."""
+  _require_device(r, y, x, info)
+  dt = np_dtype_of(r)
+  _hip.refuse_not_float(dt, 'als_solve')
+  _hip.refuse_not_float(np_dtype_of(y), 'als_solve')
+  if dt != np_dtype_of(y):
+    raise TypeError('als_solve: operands of two dtypes (%s, %s); convert with astype first' % (dt, np_dtype_of(y)))
+  if r.dim() != 2 or y.dim() != 2 or r.shape[1] != y.shape[0]:
+    raise ValueError('als_solve: shapes %s and %s do not fit' % (tuple(r.shape), tuple(y.shape)))
+  m, n = (int(v) for v in r.shape)
+  f = int(y.shape[1])
+  if not 1 <= f <= _hip.SP_ALS_MAX_F:
+    raise ValueError('als_solve: f = %d is outside 1 .. %d' % (f, _hip.SP_ALS_MAX_F))
+  if tuple(x.shape) != (m, f) or np_dtype_of(x) != dt:
+    raise ValueError('als_solve: a target of shape %s and dtype %s for %d rows and %d features of %s'
+                     % (tuple(x.shape), np_dtype_of(x), m, f, dt))
+  assert np_dtype_of(info) == np.int32
+  if m == 0:
+    return x
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  ws = _ws.get(lib.sp_als_solve_workspace_bytes(code, m, n, f, int(bool(implicit))), r.device)
+  check(lib.sp_als_solve(code, C.c_void_p(r.data_ptr()), _ld(r), m, n, C.c_void_p(y.data_ptr()), _ld(y), f, float(la),
+                         float(alpha), int(bool(implicit)), C.c_void_p(x.data_ptr()), _ld(x),
+                         C.c_void_p(info.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
+  return x
+
+
 def gather_rows(src, idx):
   """src[idx] along axis 0 for a contiguous tensor and a device int64 index vector (filter.py:50-75)."""
   _require_device(src, idx)
