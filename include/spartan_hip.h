@@ -427,8 +427,11 @@ int sp_segment_sum_counts(const void* d_points, int32_t dtype, int64_t ldx, cons
 /* sp_random_fill: the per-tile bodies of the reference's random builders
  * (spartan/expr/srandom.py:38-55, np.random.rand / randn / randint per tile) as a
  * counter-based generator: element i = Philox4x32-10(seed, offset + i), so a tile's
- * content is independent of the launch geometry.  kind 0: uniform [0,1), 1: standard
- * normal, 2: integers in [lo, hi).  dtype: SP_F32 | SP_F64 | SP_I32 | SP_I64.
+ * content is independent of the launch geometry.  Elements come in pairs (one Philox block
+ * each), so `offset` must be even: an odd one is refused before anything is launched.
+ * kind 0: uniform [0,1) (float32: float32(u), with a result of 1.0 replaced by the largest
+ * float32 below 1), 1: standard normal, 2: integers in [lo, hi).
+ * dtype: SP_F32 | SP_F64 | SP_I32 | SP_I64.
  * (Not NumPy's stream; the reference re-seeds every worker from the clock.) */
 int sp_random_fill(void* d_out, int32_t dtype, int64_t n, int32_t kind, uint64_t seed, uint64_t offset,
                    int64_t lo, int64_t hi, void* stream);
@@ -533,9 +536,10 @@ int sp_tiling_solve(int32_t n_nodes, int64_t n_edges, const int32_t* edge_u, con
                     int32_t* choice, double* total);
 
 /* sp_gather_rows: dst[i, :] = src[idx[i], :] -- integer-array indexing `x[idx]`, the tile body of _int_index_mapper
- * (spartan/expr/operator/filter.py:50-75).  Rows of row_bytes bytes (a multiple of 4, or of 2 for rows of 2-byte
- * elements), source rows
- * src_row_stride_bytes apart; idx int64 on the device, negative values count from the end. */
+ * (spartan/expr/operator/filter.py:50-75).  Rows of row_bytes bytes (any count: moved as 16-, 4-, 2- or 1-byte
+ * words, the widest that the row length, the stride and both base pointers allow), source rows
+ * src_row_stride_bytes apart; idx int64 on the device, every value in [-n_src_rows, n_src_rows) -- the caller's duty,
+ * the kernel does not check --, negative values count from the end. */
 int sp_gather_rows(const void* d_src, int64_t src_row_stride_bytes, int64_t n_src_rows, const int64_t* d_idx,
                    int64_t n_idx, int64_t row_bytes, void* d_dst, void* stream);
 

@@ -138,6 +138,10 @@ class Facade(object):
   def reshape(self, x, shape): return self.from_numpy(np.ascontiguousarray(x.glom().reshape(shape)))
   def ravel(self, x): return self.from_numpy(np.ascontiguousarray(x.glom().ravel()))
 
+  def scan(self, x, reduce_fn=np.sum, scan_fn=np.cumsum, axis=None):     # scan.py:67-97: scan_fn over the whole array
+    v = x.glom()
+    return self.from_numpy(np.ascontiguousarray(np.asarray(scan_fn(v, axis=axis)).reshape(v.shape)))
+
   # elementwise
   def sqrt(self, v): return self.map((v,), np.sqrt)
   def exp(self, v): return self.map((v,), np.exp)

@@ -1,8 +1,9 @@
 // Counter-based random fills (Philox4x32-10) for the reference's srandom builders
 // (spartan/expr/srandom.py:38-55: _make_rand / _make_randn / _make_randint run
-// np.random.* per tile).  Element i of a fill is a pure function of (seed, offset + i),
-// so a tile's content does not depend on the launch geometry; the host advances
-// `offset` by the tile size after every fill.  The values are NOT NumPy's Mersenne
+// np.random.* per tile).  Element i of a fill is a pure function of (seed, offset + i)
+// for an even `offset` (elements come in pairs, one Philox block each; an odd offset is
+// refused), so a tile's content does not depend on the launch geometry; the host advances
+// `offset` by the tile size, made even, after every fill.  The values are NOT NumPy's Mersenne
 // Twister stream (the reference re-seeds every worker from the clock,
 // srandom.py:23-35, so its values are not reproducible either).
 #include "sp_common.hpp"
@@ -40,8 +41,18 @@ __device__ __forceinline__ void uniforms53(const U4& r, double& a, double& b) {
 template <typename T> struct kIsI64 { static constexpr bool value = false; };
 template <> struct kIsI64<int64_t> { static constexpr bool value = true; };
 
+template <typename T> struct kIsF32 { static constexpr bool value = false; };
+template <> struct kIsF32<float> { static constexpr bool value = true; };
+
 template <typename T>
 __device__ __forceinline__ void put(void* out, int64_t i, double v) { ((T*)out)[i] = (T)v; }
+
+// float32 uniform: (float)u rounds to 1.0f for every u >= 1 - 2^-25; those become the largest float below 1, so
+// that the range is [0, 1) as documented (every other value is the plain cast)
+__device__ __forceinline__ double unit_f32(double u) {
+  const float f = (float)u;
+  return (double)(f < 1.0f ? f : 0x1.fffffep-1f);
+}
 
 // kind 0: uniform [0,1)   1: standard normal (Box-Muller)   2: integers in [lo, hi)
 // One thread produces elements 2t and 2t+1 from Philox block (offset/2 + t).
@@ -64,6 +75,12 @@ __global__ __launch_bounds__(256) void sp_random_kernel(void* __restrict__ out, 
       }
     } else {
       uniforms53(r, a, b);
+      if constexpr (kIsF32<T>::value) {
+        if (kind == 0) {
+          a = unit_f32(a);
+          b = unit_f32(b);
+        }
+      }
       if (kind == 1) {
         const double rad = sqrt(-2.0 * log(1.0 - a));   // 1 - a in (0, 1]
         const double ang = 6.283185307179586476925 * b;
@@ -85,11 +102,13 @@ extern "C" int sp_random_fill(void* d_out, int32_t dtype, int64_t n, int32_t kin
   if (!d_out) SP_FAIL("sp_random_fill: NULL pointer");
   if (kind < 0 || kind > 2) SP_FAIL("sp_random_fill: unknown kind %d", kind);
   if (kind == 2 && hi <= lo) SP_FAIL("sp_random_fill: empty integer range [%lld, %lld)", (long long)lo, (long long)hi);
+  if (offset & 1) SP_FAIL("sp_random_fill: odd offset %llu (elements come in pairs: a fill starts at an even position)",
+                          (unsigned long long)offset);
   const uint64_t range = kind == 2 ? (uint64_t)(hi - lo) : 1;
   int64_t blocks = ((n + 1) / 2 + 255) / 256;
   if (blocks > SP_CUS * 16) blocks = SP_CUS * 16;
   hipStream_t st = (hipStream_t)stream;
-  // element pairs are numbered from offset / 2: fills of even sizes tile one global stream
+  // element pairs are numbered from offset / 2: fills at even offsets tile one global stream
   const uint64_t base = offset / 2;
 #define SP_RAND_GO(T) \
   hipLaunchKernelGGL((sp_random_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, d_out, n, kind, seed, base, lo, range)

@@ -575,8 +575,9 @@ extern "C" int sp_cumscan(const void* d_in, void* d_out, int32_t dtype, int64_t 
 
 // ------------------------------------------------------------------ row gather (integer-array indexing)
 // dst[i, :] = src[idx[i], :] for rows of `row_bytes` bytes: the tile body of the reference's _int_index_mapper
-// (spartan/expr/operator/filter.py:50-75, one src.select(row) per index there).  One thread per 4-byte word
-// (16-byte words when the row length and both bases allow); negative indices count from the end like NumPy's.
+// (spartan/expr/operator/filter.py:50-75, one src.select(row) per index there).  One thread per word of 16, 4, 2
+// or 1 bytes (the widest that the row length, the stride and both bases allow); negative indices count from the end
+// like NumPy's.  Indices are trusted: the range check is the caller's (expr/filter.py eval_index).
 template <typename W>
 __global__ __launch_bounds__(256) void sp_gather_rows_kernel(const W* __restrict__ src, int64_t src_row_words,
                                                              const int64_t* __restrict__ idx, int64_t n_idx,
@@ -596,26 +597,24 @@ extern "C" int sp_gather_rows(const void* d_src, int64_t src_row_stride_bytes, i
   if (n_idx < 0 || row_bytes < 0 || n_src_rows < 0 || src_row_stride_bytes < row_bytes) SP_FAIL("sp_gather_rows: bad sizes");
   if (n_idx == 0 || row_bytes == 0) return 0;
   if (!d_src || !d_idx || !d_dst) SP_FAIL("sp_gather_rows: NULL pointer");
-  if (row_bytes % 2 || src_row_stride_bytes % 2) SP_FAIL("sp_gather_rows: rows must be a multiple of 2 bytes");
   hipStream_t st = (hipStream_t)stream;
-  const bool wide = row_bytes % 16 == 0 && src_row_stride_bytes % 16 == 0 && ((uintptr_t)d_src % 16) == 0 &&
-                    ((uintptr_t)d_dst % 16) == 0;
-  const bool half_words = !wide && (row_bytes % 4 || src_row_stride_bytes % 4);   // rows of 2-byte elements, odd length
-  if (half_words && (((uintptr_t)d_src | (uintptr_t)d_dst) & 1))
-    SP_FAIL("sp_gather_rows: rows of %lld bytes need 2-byte aligned pointers", (long long)row_bytes);
-  const int64_t words = wide ? row_bytes / 16 : (half_words ? row_bytes / 2 : row_bytes / 4);
+  // the widest word that the row length, the row stride and both base pointers are all multiples of
+  const uint64_t all = (uint64_t)row_bytes | (uint64_t)src_row_stride_bytes | (uint64_t)(uintptr_t)d_src | (uint64_t)(uintptr_t)d_dst;
+  const int64_t wb = all % 16 == 0 ? 16 : (all % 4 == 0 ? 4 : (all % 2 == 0 ? 2 : 1));
+  const int64_t words = row_bytes / wb;
   int64_t blocks = (n_idx * words + 255) / 256;
   const int64_t cap = (int64_t)SP_CUS * SP_BLOCKS_PER_CU * 4;
   if (blocks > cap) blocks = cap;
-  if (wide)
-    hipLaunchKernelGGL((sp_gather_rows_kernel<float4>), dim3((unsigned)blocks), dim3(256), 0, st, (const float4*)d_src,
-                       src_row_stride_bytes / 16, d_idx, n_idx, n_src_rows, words, (float4*)d_dst);
-  else if (half_words)
-    hipLaunchKernelGGL((sp_gather_rows_kernel<uint16_t>), dim3((unsigned)blocks), dim3(256), 0, st, (const uint16_t*)d_src,
-                       src_row_stride_bytes / 2, d_idx, n_idx, n_src_rows, words, (uint16_t*)d_dst);
-  else
-    hipLaunchKernelGGL((sp_gather_rows_kernel<uint32_t>), dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t*)d_src,
-                       src_row_stride_bytes / 4, d_idx, n_idx, n_src_rows, words, (uint32_t*)d_dst);
+#define SP_GATHER_GO(W)                                                                                              \
+  hipLaunchKernelGGL((sp_gather_rows_kernel<W>), dim3((unsigned)blocks), dim3(256), 0, st, (const W*)d_src,          \
+                     src_row_stride_bytes / wb, d_idx, n_idx, n_src_rows, words, (W*)d_dst)
+  switch (wb) {
+    case 16: SP_GATHER_GO(float4); break;
+    case 4: SP_GATHER_GO(uint32_t); break;
+    case 2: SP_GATHER_GO(uint16_t); break;
+    default: SP_GATHER_GO(uint8_t); break;
+  }
+#undef SP_GATHER_GO
   SP_CHECK_LAUNCH();
   return 0;
 }

@@ -45,6 +45,12 @@ def eval_index(ctx, src, idx):
                               'masked arrays are not supported on the GPU backend')
   Assert.eq(len(idx.shape), 1)
   host_idx = np.asarray(idx.glom() if isinstance(idx, distarray.DistArray) else idx).astype(np.int64)
+  # NumPy's range check, here and not in the tile body: the row gather trusts its indices (sp_gather_rows reads
+  # src[idx[i]] unchecked), so nothing out of [-n, n) may get as far as a fetch or a launch
+  n = int(src.shape[0])
+  bad = host_idx[(host_idx < -n) | (host_idx >= n)]
+  if bad.size:
+    raise IndexError('index %d is out of bounds for axis 0 with size %d' % (int(bad[0]), n))
   dst = distarray.create((int(host_idx.shape[0]),) + tuple(src.shape[1:]), dtype=src.dtype)
   return dst.map_to_array(_int_index_mapper, kw={'src': src, 'idx': host_idx, 'dst': dst})
 

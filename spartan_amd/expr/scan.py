@@ -6,11 +6,32 @@ import numpy as np
 
 from .map import map_with_location
 from .shuffle import shuffle
-from .. import context
+from .. import _hip, context
 from ..array import distarray, extent
 from ..util import divup
 
 _PAIRS = {np.sum: ('SUM', np.cumsum, False), np.prod: ('PROD', np.cumprod, True)}
+_I64 = np.dtype(np.int64)
+
+
+def _scan_dtype(dtype):
+  """The dtype np.cumsum / np.cumprod (and np.sum / np.prod) compute and return in -- what the reference's
+  `scan_fn(tile, axis)` yields (scan.py:63): floats keep theirs, bool and int32 widen to int64.  uint8 would widen to
+  uint64, which is no tile dtype, and the narrow types have no scan kernel: both are refused, before anything runs."""
+  dtype = np.dtype(dtype)
+  if dtype in (np.dtype(np.float32), np.dtype(np.float64)):
+    return dtype
+  if dtype in (np.dtype(np.bool_), np.dtype(np.int32), _I64):
+    return _I64
+  _hip.refuse_narrow(dtype, 'scan (cumsum / cumprod)')
+  raise TypeError('dtype %s is not supported by scan (cumsum / cumprod): the result would be %s (supported: float32 '
+                  'float64 int32 int64 bool); convert with astype first' % (dtype, np.cumsum(np.zeros(1, dtype)).dtype))
+
+
+def _widened(be, data):
+  """The dense tile in the dtype the scan computes in."""
+  data = _dense(data)
+  return be.astype(data, _scan_dtype(be.dtype_of(data)))
 
 
 class _Probe(object):
@@ -74,9 +95,9 @@ def _scan_reduce_mapper(array, ex, reduce_fn, axis):
   new_shape[axis] = divup(array.shape[axis], axis_shape)
   dst_ex = extent.create(new_ul, new_lr, new_shape)
   if isinstance(data, distarray.Absent) or not ctx.executing:
-    yield (dst_ex, distarray.Absent(dst_ex.shape, array.dtype))
+    yield (dst_ex, distarray.Absent(dst_ex.shape, _scan_dtype(array.dtype)))
     return
-  local = ctx.backend.reduce_axis(_dense(data), red, axis)
+  local = ctx.backend.reduce_axis(_widened(ctx.backend, data), red, axis)
   yield (dst_ex, local.reshape(dst_ex.shape))
 
 
@@ -95,7 +116,7 @@ def _scan_mapper(tile, ex, scan_fn=None, axis=None, scan_base=None, tile_shape=N
     if tile_id > 0:
       base_slice[axis] = slice(tile_id - 1, tile_id)
       base = scan_base[tuple(base_slice)]
-  out = be.cumscan(_dense(tile), axis, product)
+  out = be.cumscan(_widened(be, tile), axis, product)
   if base is not None:
     base = np.ascontiguousarray(base).astype(be.dtype_of(out))
     out = be.evaluate_fn(np.multiply if product else np.add, [out, base], {}, tuple(out.shape))
@@ -108,6 +129,7 @@ _scan_mapper._sp_tile_fn = True
 def scan(array, reduce_fn=np.sum, scan_fn=np.cumsum, axis=None):
   """Scan `array` over `axis` (None: the flattened array, result in the array's shape); scan.py:67-97."""
   red, product = _kind(reduce_fn, scan_fn)
+  _scan_dtype(array.evaluate().dtype)      # (refusals: before any tile is reduced or scanned)
   reduce_result = shuffle(array, fn=_scan_reduce_mapper,
                           kw={'axis': axis if axis is not None else 1, 'reduce_fn': reduce_fn},
                           shape_hint=array.shape)

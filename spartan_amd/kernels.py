@@ -485,8 +485,6 @@ def gather_rows(src, idx):
   n = int(idx.numel())
   row = int(np.prod(src.shape[1:], dtype=np.int64)) * _elsize(src)
   out = devarray.empty((n,) + tuple(src.shape[1:]), np_dtype_of(src))
-  if row % 4 and (row % 2 or _elsize(src) != 2):
-    raise _hip.HipError('gather_rows: rows of %d bytes (need a multiple of 4)' % row)
   check(_hip.lib().sp_gather_rows(C.c_void_p(src.data_ptr()), row, int(src.shape[0]), C.c_void_p(idx.data_ptr()), n, row,
                                   C.c_void_p(out.data_ptr()), _stream()))
   return out

@@ -117,6 +117,15 @@ def prepare_tree():
   sub(S + 'expr/creation.py', [("dtype=np.float,", "dtype=float,"),
                                # a LIST of slices as an index meant the tuple of them until NumPy 1.23
                                ("result = tile[slices].diagonal()", "result = tile[tuple(slices)].diagonal()")])
+  # scan.py: integer `/` on tile indices, and a LIST of slices as an index (the tuple of them until NumPy 1.23)
+  sub(S + 'expr/operator/scan.py', [
+      ("  id = (ex.lr[axis]-1) / axis_shape", "  id = (ex.lr[axis]-1) // axis_shape"),
+      ("    tile_id = (ex[1][axis] - 1) / tile_shape[axis]\n    base_slice[axis] = slice(tile_id, tile_id+1)",
+       "    tile_id = (ex[1][axis] - 1) // tile_shape[axis]\n    base_slice[axis] = slice(tile_id, tile_id+1)"),
+      ("    tile_id = (ex[1][axis] - 1) / tile_shape[axis]\n    if tile_id > 0:",
+       "    tile_id = (ex[1][axis] - 1) // tile_shape[axis]\n    if tile_id > 0:"),
+      ("tile[new_slice] += scan_base[base_slice]", "tile[tuple(new_slice)] += scan_base[tuple(base_slice)]"),
+  ])
   # `a / b` on expressions: only __div__/__rdiv__ exist (base.py:348-349,387-388)
   sub(S + 'expr/operator/base.py', [
       ("  def __eq__(self, other):\n    return _map(self, other, fn=np.equal)",

@@ -285,6 +285,23 @@ def programs():
        lambda: None, None))
   add(('uint8_like_bool_sum', lambda sp: sp.sum(sp.from_numpy((np.arange(300 * 4).reshape(300, 4) % 3 == 0)), 0), lambda: None, None))
   add(('int64_mean_axis0', lambda sp: sp.mean(sp.from_numpy(np.arange(50 * 4, dtype=np.int64).reshape(50, 4) * 3), 0), lambda: None, None))
+  # ---- scan (tests/test_scan.py; operator/scan.py): the result has the dtype np.cumsum / np.cumprod return -- float32
+  # stays, int32 and bool become int64.  Whole-valued inputs: exact in any order.  (The bool and cumprod programs scan
+  # the short axis of a tall array, which no worker count splits: where the scanned axis is split the reference adds
+  # the preceding total in place -- a TypeError for a bool tile under NumPy 2 (as is the flattened scan of an int32 one,
+  # whose total is a float64), and a sum where cumprod needs a product.)
+  def scan_src(dtype):
+    v = np.arange(48 * 20).reshape(48, 20)
+    if np.dtype(dtype) == np.bool_:
+      return v % 3 == 0
+    return (v % 7 - 3).astype(dtype)
+  add(('scan_f32_axis0', lambda sp: sp.scan(sp.from_numpy(scan_src(F32)), axis=0), lambda: np.cumsum(scan_src(F32), 0), None))
+  add(('scan_f32_axis1', lambda sp: sp.scan(sp.from_numpy(scan_src(F32)), axis=1), lambda: np.cumsum(scan_src(F32), 1), None))
+  add(('scan_f32_flat', lambda sp: sp.scan(sp.from_numpy(scan_src(F32))), lambda: np.cumsum(scan_src(F32)).reshape(48, 20), None))
+  add(('scan_int32_axis0', lambda sp: sp.scan(sp.from_numpy(scan_src(np.int32)), axis=0), lambda: np.cumsum(scan_src(np.int32), 0), None))
+  add(('scan_bool_axis1', lambda sp: sp.scan(sp.from_numpy(scan_src(np.bool_)), axis=1), lambda: np.cumsum(scan_src(np.bool_), 1), None))
+  add(('scan_cumprod_axis1', lambda sp: sp.scan(sp.from_numpy(scan_src(np.int32) % 3 + 1), np.prod, np.cumprod, axis=1),
+       lambda: np.cumprod(scan_src(np.int32) % 3 + 1, 1), None))
   return P
 
 
