@@ -280,12 +280,14 @@ EXPORTS_GRAPH = ['sp_apsp', 'sp_graph_from_knn']
 # every symbol include/spartan_hip_als.h declares (the same library), and its SP_ALS_MAX_F
 EXPORTS_ALS = ['sp_als_solve', 'sp_als_solve_workspace_bytes']
 SP_ALS_MAX_F = 64
+# every symbol include/spartan_hip_fuzzy.h declares (the same library)
+EXPORTS_FUZZY = ['sp_fuzzy_step', 'sp_fuzzy_step_workspace_bytes']
 _extras = None
 
 
 def extras():
-  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve); raises if it has not been
-  built."""
+  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve, fuzzy_step); raises if it
+  has not been built."""
   global _extras
   if _extras is None:
     lib()
@@ -311,6 +313,9 @@ def extras():
     x.sp_als_solve_workspace_bytes.argtypes = [i32, i64, i64, i32, i32]
     x.sp_als_solve_workspace_bytes.restype = sz
     x.sp_als_solve.argtypes = [i32, vp, i64, i64, i64, vp, i64, i32, C.c_double, C.c_double, i32, vp, i64, vp, vp, sz, vp]
+    x.sp_fuzzy_step_workspace_bytes.argtypes = [i32, i64, i64, i64, i32]
+    x.sp_fuzzy_step_workspace_bytes.restype = sz
+    x.sp_fuzzy_step.argtypes = [i32, vp, i64, i64, vp, i64, i64, i64, C.c_double, i32, vp, vp, i64, vp, vp, i64, vp, sz, vp]
     x.sp_apsp.argtypes = [i32, vp, i64, i64, vp, vp]
     x.sp_graph_from_knn.argtypes = [i32, vp, vp, i64, i64, i64, vp, i64, vp]
     _extras = x

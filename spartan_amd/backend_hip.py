@@ -1344,6 +1344,38 @@ class HipBackend(object):
       kernels.als_solve(ratings, factors, la, alpha, implicit, out, info)
     return out
 
+  def fuzzy_step(self, points, centers, m, want_u=False, splits=0):
+    """One iteration of the reference's fuzzy k-means on a row tile as NEW tensors (labels int64 [n], sums [k, d],
+    wsum [k]), plus u [n, k] when `want_u` is set (sp_fuzzy_step: distances, memberships and the weighted sums fused;
+    without `want_u` nothing of size n x k is allocated or written).  With dist_ij = |x_i - c_j| (1e-10 where it is 0)
+    and p = dist ^ (1 / (m - 1)):  u_ij = p_ij / sum_j p_ij,  labels_i = the lowest j at the largest distance,
+    w = u ^ m,  sums = w^T . points,  wsum_j = sum_i w_ij.  Both operands fp32 or both fp64; m finite and > 1; k >= 1.
+    splits: into how many ranges the rows are cut (0: the library chooses); labels and u do not depend on it, bit for
+    bit.  The call counts as one launch and never waits for the device."""
+    points, centers = self._as_device(points), self._as_device(centers)
+    dt = self.dtype_of(points)
+    for t in (points, centers):
+      _hip.refuse_not_float(self.dtype_of(t), 'fuzzy_step')
+    if dt != self.dtype_of(centers):
+      raise TypeError('fuzzy_step: operands of two dtypes (%s, %s); convert with astype first'
+                      % (dt, self.dtype_of(centers)))
+    m = float(m)
+    if not (m > 1.0 and m != float('inf')):
+      raise ValueError('fuzzy_step: m = %r must be finite and > 1' % (m,))
+    if points.dim() != 2 or centers.dim() != 2 or points.shape[1] != centers.shape[1]:
+      raise ValueError('fuzzy_step: shapes %s and %s do not fit' % (tuple(points.shape), tuple(centers.shape)))
+    n, d = (int(v) for v in points.shape)
+    k = int(centers.shape[0])
+    if k < 1:
+      raise ValueError('fuzzy_step: k = %d must be at least 1' % k)
+    labels, sums, wsum = self.empty((n,), np.int64), self.empty((k, d), dt), self.empty((k,), dt)
+    u = self.empty((n, k), dt) if want_u else None
+    before = self.launches
+    points, centers = self._knn_rows(points), self._knn_rows(centers)
+    self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
+    kernels.fuzzy_step(points, centers, m, labels, sums, wsum, u=u, splits=splits)
+    return (labels, sums, wsum, u) if want_u else (labels, sums, wsum)
+
   def convolve(self, image, filters):
     """stencil.py:29-45 as a GEMM: P[(n, x, y), (c, i, j)] = image[n, c, x+i, y+j] (0 beyond the edge) by one strided
     box copy per (c, i, j); P . filters[(c, i, j), f] on the MFMA GEMM; back to [n, f, x, y]."""

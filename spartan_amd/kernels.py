@@ -478,6 +478,49 @@ def als_solve(r, y, la, alpha, implicit, x, info):
   return x
 
 
+def fuzzy_step(points, centers, m, labels, sums, wsum, u=None, splits=0):
+  """One iteration of the reference's fuzzy k-means on a row tile (sp_fuzzy_step; include/spartan_hip_fuzzy.h states
+  the arithmetic and its order): `points` [n, d] and `centers` [k, d], both fp32 or both fp64, views with inner stride
+  1; labels [n] int64 contiguous (or None) <- the lowest centre at the largest distance, sums [k, d] (a view with inner
+  stride 1) <- sum_i w_ij x_i, wsum [k] contiguous <- sum_i w_ij, and, only if `u` [n, k] (a view with inner stride 1)
+  is passed, u <- the memberships.  splits: 0 = the library chooses into how many ranges the rows are cut, s >= 1 =
+  min(s, ceil(n / 64)) ranges.  TypeError for other or mixed dtypes, ValueError for m that is not finite and > 1,
+  k < 1 or shapes that do not fit -- all before any launch.  Nothing waits for the device."""
+  _require_device(points, centers, labels, sums, wsum, u)
+  dt = np_dtype_of(points)
+  for t in (points, centers, sums, wsum) + (() if u is None else (u,)):
+    _hip.refuse_not_float(np_dtype_of(t), 'fuzzy_step')
+    if np_dtype_of(t) != dt:
+      raise TypeError('fuzzy_step: operands of two dtypes (%s, %s); convert with astype first' % (dt, np_dtype_of(t)))
+  m = float(m)
+  if not (m > 1.0 and m != float('inf')):
+    raise ValueError('fuzzy_step: m = %r must be finite and > 1' % (m,))
+  if points.dim() != 2 or centers.dim() != 2 or points.shape[1] != centers.shape[1]:
+    raise ValueError('fuzzy_step: shapes %s and %s do not fit' % (tuple(points.shape), tuple(centers.shape)))
+  n, d = (int(v) for v in points.shape)
+  k = int(centers.shape[0])
+  if k < 1:
+    raise ValueError('fuzzy_step: k = %d must be at least 1' % k)
+  if int(splits) < 0:
+    raise ValueError('fuzzy_step: splits = %d' % splits)
+  if tuple(sums.shape) != (k, d) or tuple(wsum.shape) != (k,) or (u is not None and tuple(u.shape) != (n, k)):
+    raise ValueError('fuzzy_step: targets of shapes %s, %s, %s for %d rows, %d centres and %d features'
+                     % (tuple(sums.shape), tuple(wsum.shape), None if u is None else tuple(u.shape), n, k, d))
+  if labels is not None and (tuple(labels.shape) != (n,) or np_dtype_of(labels) != np.int64):
+    raise ValueError('fuzzy_step: labels of shape %s and dtype %s for %d rows' % (tuple(labels.shape), np_dtype_of(labels), n))
+  assert wsum.is_contiguous() and (labels is None or labels.is_contiguous())
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  ws = _ws.get(lib.sp_fuzzy_step_workspace_bytes(code, n, k, d, int(splits)), points.device)
+  check(lib.sp_fuzzy_step(code, C.c_void_p(points.data_ptr()), _ld(points), n, C.c_void_p(centers.data_ptr()),
+                          _ld(centers), k, d, m, int(splits),
+                          None if labels is None else C.c_void_p(labels.data_ptr()), C.c_void_p(sums.data_ptr()),
+                          _ld(sums), C.c_void_p(wsum.data_ptr()),
+                          None if u is None else C.c_void_p(u.data_ptr()), k if u is None else _ld(u),
+                          C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
+  return labels, sums, wsum, u
+
+
 def gather_rows(src, idx):
   """src[idx] along axis 0 for a contiguous tensor and a device int64 index vector (filter.py:50-75)."""
   _require_device(src, idx)
