@@ -282,12 +282,15 @@ EXPORTS_ALS = ['sp_als_solve', 'sp_als_solve_workspace_bytes']
 SP_ALS_MAX_F = 64
 # every symbol include/spartan_hip_fuzzy.h declares (the same library)
 EXPORTS_FUZZY = ['sp_fuzzy_step', 'sp_fuzzy_step_workspace_bytes']
+# every symbol include/spartan_hip_lda.h declares (the same library), and its SP_LDA_MAX_K
+EXPORTS_LDA = ['sp_lda_step', 'sp_lda_step_workspace_bytes']
+SP_LDA_MAX_K = 128
 _extras = None
 
 
 def extras():
-  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve, fuzzy_step); raises if it
-  has not been built."""
+  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve, fuzzy_step, lda_step);
+  raises if it has not been built."""
   global _extras
   if _extras is None:
     lib()
@@ -316,6 +319,9 @@ def extras():
     x.sp_fuzzy_step_workspace_bytes.argtypes = [i32, i64, i64, i64, i32]
     x.sp_fuzzy_step_workspace_bytes.restype = sz
     x.sp_fuzzy_step.argtypes = [i32, vp, i64, i64, vp, i64, i64, i64, C.c_double, i32, vp, vp, i64, vp, vp, i64, vp, sz, vp]
+    x.sp_lda_step_workspace_bytes.argtypes = [i32, i64, i64, i64, i32, i32]
+    x.sp_lda_step_workspace_bytes.restype = sz
+    x.sp_lda_step.argtypes = [i32, vp, i64, i64, i64, vp, i64, i64, C.c_double, C.c_double, i32, i32, vp, i64, vp, i64, vp, sz, vp]
     x.sp_apsp.argtypes = [i32, vp, i64, i64, vp, vp]
     x.sp_graph_from_knn.argtypes = [i32, vp, vp, i64, i64, i64, vp, i64, vp]
     _extras = x

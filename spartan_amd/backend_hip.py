@@ -1376,6 +1376,35 @@ class HipBackend(object):
     kernels.fuzzy_step(points, centers, m, labels, sums, wsum, u=u, splits=splits)
     return (labels, sums, wsum, u) if want_u else (labels, sums, wsum)
 
+  def lda_step(self, x, n, alpha, eta, iters, want_delta=True, want_doc_topics=True, splits=0):
+    """The tile body of the reference's LDA (CVB0) on a tile of documents as NEW tensors (delta [k, V], doc_topics
+    [D, k]; None in the place of one that is not wanted): `x` [V, D] terms x documents, `n` [k, V] the whole topic /
+    term counts (sp_lda_step: the per-document loops fused, nothing of size V x D is allocated).  Per document gamma
+    starts at 1 / k and is renewed `iters` times from q_tj = x_j p_tj / sum_t p_tj with p_tj = (n_tj + eta)
+    (gamma_t + alpha) / (sum_j |n_tj| + eta V); doc_topics is the last gamma (a row of NaN for a document without a
+    term), delta the sum over the documents of the last iteration's q.  Both operands fp32 or both fp64; 1 <= k <= 128,
+    iters >= 1, alpha and eta finite and > 0.  splits: into how many ranges the documents are cut (0: the library
+    chooses); doc_topics does not depend on it, bit for bit.  The call counts as one launch and never waits for the
+    device."""
+    x, n = self._as_device(x), self._as_device(n)
+    dt = self.dtype_of(x)
+    for t in (x, n):
+      _hip.refuse_not_float(self.dtype_of(t), 'lda_step')
+    if dt != self.dtype_of(n):
+      raise TypeError('lda_step: operands of two dtypes (%s, %s); convert with astype first' % (dt, self.dtype_of(n)))
+    if x.dim() != 2 or n.dim() != 2 or x.shape[0] != n.shape[1]:
+      raise ValueError('lda_step: shapes %s and %s do not fit' % (tuple(x.shape), tuple(n.shape)))
+    v, d = (int(s) for s in x.shape)
+    k = int(n.shape[0])
+    kernels.check_lda_params(k, alpha, eta, iters)
+    delta = self.empty((k, v), dt) if want_delta else None
+    doc_topics = self.empty((d, k), dt) if want_doc_topics else None
+    before = self.launches
+    x, n = self._knn_rows(x), self._knn_rows(n)
+    self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
+    kernels.lda_step(x, n, alpha, eta, iters, delta=delta, doc_topics=doc_topics, splits=splits)
+    return delta, doc_topics
+
   def convolve(self, image, filters):
     """stencil.py:29-45 as a GEMM: P[(n, x, y), (c, i, j)] = image[n, c, x+i, y+j] (0 beyond the edge) by one strided
     box copy per (c, i, j); P . filters[(c, i, j), f] on the MFMA GEMM; back to [n, f, x, y]."""

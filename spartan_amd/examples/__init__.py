@@ -7,5 +7,7 @@ symmetric eigenproblem of the small B . B^T on sp_syevj) and `pca` (PCA on that 
 `sklearn.neighbors.NearestNeighbors` searches row bands of X with sp_knn and merges their candidates with sp_knn_merge;
 `sklearn.manifold.Isomap` turns its lists into a graph (sp_graph_from_knn), takes all-pairs shortest paths (sp_apsp) and
 embeds with sp_syevj; `als` (alternating least squares) solves every row's normal equations of a half-step in sp_als_solve;
-`fuzzy_kmeans` runs one sp_fuzzy_step (memberships, labels and weighted sums fused) per row tile and iteration.
+`fuzzy_kmeans` runs one sp_fuzzy_step (memberships, labels and weighted sums fused) per row tile and iteration;
+`lda.learn_topics` (LDA by collapsed variational Bayes) runs one sp_lda_step (the per-document loops fused) per tile of
+documents and pass.
 Like `sort` they are imported on first use, not with the package."""

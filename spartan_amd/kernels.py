@@ -521,6 +521,56 @@ def fuzzy_step(points, centers, m, labels, sums, wsum, u=None, splits=0):
   return labels, sums, wsum, u
 
 
+def check_lda_params(k, alpha, eta, iters, what='lda_step'):
+  """(alpha, eta, iters) as the library takes them, or ValueError for what sp_lda_step refuses."""
+  alpha, eta = float(alpha), float(eta)
+  if not 1 <= int(k) <= _hip.SP_LDA_MAX_K:
+    raise ValueError('%s: k = %d must be in 1 .. %d' % (what, int(k), _hip.SP_LDA_MAX_K))
+  if int(iters) < 1:
+    raise ValueError('%s: iters = %d must be at least 1' % (what, int(iters)))
+  if not (alpha > 0.0 and alpha != float('inf')):
+    raise ValueError('%s: alpha = %r must be finite and > 0' % (what, alpha))
+  if not (eta > 0.0 and eta != float('inf')):
+    raise ValueError('%s: eta = %r must be finite and > 0' % (what, eta))
+  return alpha, eta, int(iters)
+
+
+def lda_step(x, n, alpha, eta, iters, delta=None, doc_topics=None, splits=0):
+  """One CVB0 step of the reference's LDA on a tile of documents (sp_lda_step; include/spartan_hip_lda.h states the
+  arithmetic and its order): `x` [V, D] terms x documents and `n` [k, V] topic / term counts, both fp32 or both fp64,
+  views with inner stride 1; delta [k, V] (a view with inner stride 1, or None) <- the sum over the documents of the
+  last inner iteration's q, doc_topics [D, k] (the same, or None) <- gamma, NaN rows for empty documents.  splits:
+  0 = the library chooses into how many ranges the documents are cut, s >= 1 = min(s, ceil(D / 64)) ranges.  TypeError
+  for other or mixed dtypes, ValueError for k outside 1 .. 128, iters < 1, alpha or eta not finite and > 0 or shapes
+  that do not fit -- all before any launch.  Nothing waits for the device."""
+  _require_device(x, n, delta, doc_topics)
+  dt = np_dtype_of(x)
+  for t in (x, n) + tuple(o for o in (delta, doc_topics) if o is not None):
+    _hip.refuse_not_float(np_dtype_of(t), 'lda_step')
+    if np_dtype_of(t) != dt:
+      raise TypeError('lda_step: operands of two dtypes (%s, %s); convert with astype first' % (dt, np_dtype_of(t)))
+  if x.dim() != 2 or n.dim() != 2 or x.shape[0] != n.shape[1]:
+    raise ValueError('lda_step: shapes %s and %s do not fit' % (tuple(x.shape), tuple(n.shape)))
+  v, d = (int(s) for s in x.shape)
+  k = int(n.shape[0])
+  alpha, eta, iters = check_lda_params(k, alpha, eta, iters)
+  if int(splits) < 0:
+    raise ValueError('lda_step: splits = %d' % splits)
+  if (delta is not None and tuple(delta.shape) != (k, v)) or (doc_topics is not None and tuple(doc_topics.shape) != (d, k)):
+    raise ValueError('lda_step: targets of shapes %s, %s for %d terms, %d documents and %d topics'
+                     % (None if delta is None else tuple(delta.shape),
+                        None if doc_topics is None else tuple(doc_topics.shape), v, d, k))
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  ws = _ws.get(lib.sp_lda_step_workspace_bytes(code, v, d, k, iters, int(splits)), x.device)
+  check(lib.sp_lda_step(code, C.c_void_p(x.data_ptr()), _ld(x), v, d, C.c_void_p(n.data_ptr()), _ld(n), k, alpha, eta,
+                        iters, int(splits),
+                        None if delta is None else C.c_void_p(delta.data_ptr()), v if delta is None else _ld(delta),
+                        None if doc_topics is None else C.c_void_p(doc_topics.data_ptr()),
+                        k if doc_topics is None else _ld(doc_topics), C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
+  return delta, doc_topics
+
+
 def gather_rows(src, idx):
   """src[idx] along axis 0 for a contiguous tensor and a device int64 index vector (filter.py:50-75)."""
   _require_device(src, idx)
