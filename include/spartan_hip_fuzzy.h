@@ -60,7 +60,7 @@ extern "C" {
  *                            workgroups carry wsum.  The distances are thus computed 1 + ceil(d / 128) times per call
  *                            (3 n k d flops each time, beside the 2 n k d of the sums): the price of keeping d unbounded
  *                            with the accumulators in registers.
- *   fuzzy_combine_kernel     only with more than one range.
+ *   sp_partial_sum_kernel    only with more than one range.
  *   d_ws    sp_fuzzy_step_workspace_bytes(...) bytes for the same arguments (never 0 for arguments that are taken). */
 size_t sp_fuzzy_step_workspace_bytes(int32_t dtype, int64_t n, int64_t k, int64_t d, int32_t splits);
 int sp_fuzzy_step(int32_t dtype, const void* d_X, int64_t ldx, int64_t n, const void* d_C, int64_t ldc, int64_t k,

@@ -84,7 +84,7 @@ extern "C" {
  *                       B and X, the next sub-block in flight in registers, recomputes the S tile, forms the signed
  *                       quotient, and accumulates acc [64 terms, KP] in registers, a thread 4 terms x KP / 16 topics; it
  *                       multiplies by A at the end.
- *   lda_combine_kernel  only with more than one range (and to write the zeros of D = 0).
+ *   sp_partial_sum_kernel  only with more than one range (and to write the zeros of D = 0).
  * Cost: S is computed iters + 1 times (iters without delta), 2 V D KP flops each, beside the 2 V D KP of each
  * accumulation: the price of storing nothing of size V x D.
  *   d_ws    sp_lda_step_workspace_bytes(...) bytes for the same arguments (never 0 for arguments that are taken): A,

@@ -267,24 +267,57 @@ def source_sha():
   return h.hexdigest()[:16]
 
 
-# every symbol include/spartan_hip_extras.h declares (libspartan_hip_extras.so: `make extras`)
 EXTRAS_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), 'libspartan_hip_extras.so')
-EXPORTS_EXTRAS = ['sp_sort_rows_workspace_bytes', 'sp_sort_rows', 'sp_potrf_workspace_bytes', 'sp_potrf', 'sp_trsm_rlt']
-# every symbol include/spartan_hip_eig.h declares (the same library)
-EXPORTS_EIG = ['sp_syevj_workspace_bytes', 'sp_syevj']
-# every symbol include/spartan_hip_knn.h declares (the same library), and its SP_KNN_MAX_K
-EXPORTS_KNN = ['sp_knn_workspace_bytes', 'sp_knn', 'sp_knn_merge']
-KNN_MAX_K = 128
-# every symbol include/spartan_hip_graph.h declares (the same library)
-EXPORTS_GRAPH = ['sp_apsp', 'sp_graph_from_knn']
-# every symbol include/spartan_hip_als.h declares (the same library), and its SP_ALS_MAX_F
-EXPORTS_ALS = ['sp_als_solve', 'sp_als_solve_workspace_bytes']
-SP_ALS_MAX_F = 64
-# every symbol include/spartan_hip_fuzzy.h declares (the same library)
-EXPORTS_FUZZY = ['sp_fuzzy_step', 'sp_fuzzy_step_workspace_bytes']
-# every symbol include/spartan_hip_lda.h declares (the same library), and its SP_LDA_MAX_K
-EXPORTS_LDA = ['sp_lda_step', 'sp_lda_step_workspace_bytes']
-SP_LDA_MAX_K = 128
+_vp, _i32, _i64, _sz, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_double
+# libspartan_hip_extras.so (`make extras`): header -> every symbol it declares -> (restype, argtypes).  The EXPORTS_*
+# lists below are read off this table, so a name cannot be exported without a signature.
+_EXTRAS_ABI = {
+    'spartan_hip_extras.h': {
+        'sp_sort_rows_workspace_bytes': (_sz, [_i32, _i64, _i64]),
+        'sp_sort_rows': (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+        'sp_potrf_workspace_bytes': (_sz, [_i32, _i64]),
+        'sp_potrf': (C.c_int, [_i32, _vp, _i64, _i64, _vp, _sz, _vp, _vp]),
+        'sp_trsm_rlt': (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
+    },
+    'spartan_hip_eig.h': {
+        'sp_syevj_workspace_bytes': (_sz, [_i32, _i64]),
+        'sp_syevj': (C.c_int, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _sz, _vp, C.POINTER(C.c_int32), _vp]),
+    },
+    'spartan_hip_knn.h': {
+        'sp_knn_workspace_bytes': (_sz, [_i32, _i64, _i64, _i64, _i32, _i32]),
+        'sp_knn': (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+        'sp_knn_merge': (C.c_int, [_i32, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    },
+    'spartan_hip_graph.h': {
+        'sp_apsp': (C.c_int, [_i32, _vp, _i64, _i64, _vp, _vp]),
+        'sp_graph_from_knn': (C.c_int, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    },
+    'spartan_hip_als.h': {
+        'sp_als_solve': (C.c_int, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _f64, _f64, _i32, _vp, _i64, _vp, _vp, _sz,
+                                   _vp]),
+        'sp_als_solve_workspace_bytes': (_sz, [_i32, _i64, _i64, _i32, _i32]),
+    },
+    'spartan_hip_fuzzy.h': {
+        'sp_fuzzy_step': (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _f64, _i32, _vp, _vp, _i64, _vp, _vp, _i64,
+                                    _vp, _sz, _vp]),
+        'sp_fuzzy_step_workspace_bytes': (_sz, [_i32, _i64, _i64, _i64, _i32]),
+    },
+    'spartan_hip_lda.h': {
+        'sp_lda_step': (C.c_int, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _f64, _f64, _i32, _i32, _vp, _i64, _vp, _i64,
+                                  _vp, _sz, _vp]),
+        'sp_lda_step_workspace_bytes': (_sz, [_i32, _i64, _i64, _i64, _i32, _i32]),
+    },
+}
+EXPORTS_EXTRAS = list(_EXTRAS_ABI['spartan_hip_extras.h'])
+EXPORTS_EIG = list(_EXTRAS_ABI['spartan_hip_eig.h'])
+EXPORTS_KNN = list(_EXTRAS_ABI['spartan_hip_knn.h'])
+EXPORTS_GRAPH = list(_EXTRAS_ABI['spartan_hip_graph.h'])
+EXPORTS_ALS = list(_EXTRAS_ABI['spartan_hip_als.h'])
+EXPORTS_FUZZY = list(_EXTRAS_ABI['spartan_hip_fuzzy.h'])
+EXPORTS_LDA = list(_EXTRAS_ABI['spartan_hip_lda.h'])
+KNN_MAX_K = 128       # SP_KNN_MAX_K of spartan_hip_knn.h
+SP_ALS_MAX_F = 64     # of spartan_hip_als.h
+SP_LDA_MAX_K = 128    # of spartan_hip_lda.h
 _extras = None
 
 
@@ -298,32 +331,10 @@ def extras():
       raise HipLibraryMissing('%s not found: build it with `make -C spartan_amd/csrc extras` (or '
                               '__graft_entry__.build())' % EXTRAS_LIB_PATH)
     x = C.CDLL(EXTRAS_LIB_PATH)
-    vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
-    x.sp_sort_rows_workspace_bytes.argtypes = [i32, i64, i64]
-    x.sp_sort_rows_workspace_bytes.restype = sz
-    x.sp_sort_rows.argtypes = [vp, i32, i64, i64, vp, vp, vp, sz, vp]
-    x.sp_potrf_workspace_bytes.argtypes = [i32, i64]
-    x.sp_potrf_workspace_bytes.restype = sz
-    x.sp_potrf.argtypes = [i32, vp, i64, i64, vp, sz, vp, vp]
-    x.sp_trsm_rlt.argtypes = [i32, vp, i64, i64, vp, i64, i64, vp]
-    x.sp_syevj_workspace_bytes.argtypes = [i32, i64]
-    x.sp_syevj_workspace_bytes.restype = sz
-    x.sp_syevj.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, sz, vp, C.POINTER(C.c_int32), vp]
-    x.sp_knn_workspace_bytes.argtypes = [i32, i64, i64, i64, i32, i32]
-    x.sp_knn_workspace_bytes.restype = sz
-    x.sp_knn.argtypes = [i32, vp, i64, i64, vp, i64, i64, i64, i32, i64, i32, vp, vp, vp, sz, vp]
-    x.sp_knn_merge.argtypes = [i32, vp, vp, i64, i64, i64, i32, vp, vp, vp]
-    x.sp_als_solve_workspace_bytes.argtypes = [i32, i64, i64, i32, i32]
-    x.sp_als_solve_workspace_bytes.restype = sz
-    x.sp_als_solve.argtypes = [i32, vp, i64, i64, i64, vp, i64, i32, C.c_double, C.c_double, i32, vp, i64, vp, vp, sz, vp]
-    x.sp_fuzzy_step_workspace_bytes.argtypes = [i32, i64, i64, i64, i32]
-    x.sp_fuzzy_step_workspace_bytes.restype = sz
-    x.sp_fuzzy_step.argtypes = [i32, vp, i64, i64, vp, i64, i64, i64, C.c_double, i32, vp, vp, i64, vp, vp, i64, vp, sz, vp]
-    x.sp_lda_step_workspace_bytes.argtypes = [i32, i64, i64, i64, i32, i32]
-    x.sp_lda_step_workspace_bytes.restype = sz
-    x.sp_lda_step.argtypes = [i32, vp, i64, i64, i64, vp, i64, i64, C.c_double, C.c_double, i32, i32, vp, i64, vp, i64, vp, sz, vp]
-    x.sp_apsp.argtypes = [i32, vp, i64, i64, vp, vp]
-    x.sp_graph_from_knn.argtypes = [i32, vp, vp, i64, i64, i64, vp, i64, vp]
+    for symbols in _EXTRAS_ABI.values():
+      for name, (restype, argtypes) in symbols.items():
+        fn = getattr(x, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _extras = x
   return _extras
 

@@ -14,13 +14,13 @@
 //                          Then the groups' accumulators are added in group order into the packed lower triangle in
 //                          LDS (over the staging area), the diagonal terms are added and the wave factors and solves
 //                          with lane p on row p.
-//   als_gram_*             implicit mode's Y^T Y: partial Grams over fixed ranges of items, then their sum in
-//                          ascending order.
+//   als_gram_partial_kernel  implicit mode's Y^T Y: partial Grams over fixed ranges of items, then their sum in
+//                          ascending order (sp_partial_sum_kernel, sp_extras_common.hpp; 0 for n = 0).
 //   als_info_kernel        hands the lowest failing row of the call to *d_info if that is still 0.
 // Vector pipe only; every sum is an explicit fma onto an accumulator that starts at 0.
 #include <limits>
 
-#include "sp_common.hpp"
+#include "sp_extras_common.hpp"
 #include "../../include/spartan_hip_als.h"
 
 namespace {
@@ -30,21 +30,6 @@ constexpr int CH = 64;         // items per chunk
 constexpr int SMALL_F = 32;    // f <= SMALL_F: 4 x 4 blocks; above: 8 x 8
 constexpr int FLAG_BYTES = 256;           // head of the workspace: the word that collects the lowest failing row
 constexpr int GRAM_RANGES = 1024;         // at most this many item ranges in the Y^T Y pre-pass
-
-template <typename T, int B>
-struct alignas(16) VecB {          // B features of one item: 16-byte aligned in LDS (fp is a multiple of B >= 4)
-  T v[B];
-};
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ __forceinline__ float sqrt_t(float a) { return __builtin_sqrtf(a); }
-__device__ __forceinline__ double sqrt_t(double a) { return __builtin_sqrt(a); }
 
 __host__ __device__ __forceinline__ int tri(int p) { return p * (p + 1) / 2; }
 
@@ -146,7 +131,8 @@ __global__ __launch_bounds__(256) void als_rows_kernel(const T* __restrict__ R, 
       if (r != (T)0) {
         const T* yp = ys + it * fp + bp * B;
         const T* yq = ys + it * fp + bq * B;
-        const VecB<T, B> lp = *reinterpret_cast<const VecB<T, B>*>(yp), lq = *reinterpret_cast<const VecB<T, B>*>(yq);
+        // B features of one item: 16-byte aligned in LDS (fp is a multiple of B >= 4)
+        const VecN<T, B> lp = *reinterpret_cast<const VecN<T, B>*>(yp), lq = *reinterpret_cast<const VecN<T, B>*>(yq);
         const T* vp = lp.v;
         const T* vq = lq.v;
         const T w = implicit ? alpha * r : (T)1;
@@ -182,7 +168,7 @@ __global__ __launch_bounds__(256) void als_rows_kernel(const T* __restrict__ R, 
         if (diag) bw[p] = g2 == 0 ? bacc[a] : bw[p] + bacc[a];
       }
     }
-    wave_sync();
+    sp_wave_sync();
   }
   if (!have_row) return;                  // (a whole wave; nothing below synchronises the workgroup)
 
@@ -194,13 +180,13 @@ __global__ __launch_bounds__(256) void als_rows_kernel(const T* __restrict__ R, 
   if (implicit) {
     for (int p = 0; p < f; ++p)
       if (lane <= p) Aw[tri(p) + lane] = Aw[tri(p) + lane] + gram[p * f + lane];
-    wave_sync();
+    sp_wave_sync();
     if (lane < f) Aw[tri(lane) + lane] = Aw[tri(lane) + lane] + la;
   } else {
     const T ridge = la * (T)count;
     if (lane < f) Aw[tri(lane) + lane] = Aw[tri(lane) + lane] + ridge;
   }
-  wave_sync();
+  sp_wave_sync();
 
   // Cholesky, left-looking: lane p owns row p; column k of L needs columns 0 .. k - 1
   const int p = lane;
@@ -216,7 +202,7 @@ __global__ __launch_bounds__(256) void als_rows_kernel(const T* __restrict__ R, 
     if (!(d > (T)0)) { bad = true; break; }                 // (wave-uniform; false for NaN)
     const T sd = sqrt_t(d);
     if (mine && p >= k) Aw[tri(p) + k] = p == k ? sd : v / sd;      // (column k: read by nobody in this step)
-    wave_sync();
+    sp_wave_sync();
   }
   T z = mine ? bw[p] : (T)0;
   if (__ballot(!(z - z == (T)0)) != 0) bad = true;           // b_i is not finite (a NaN rating in explicit mode)
@@ -274,23 +260,10 @@ __global__ __launch_bounds__(256) void als_gram_partial_kernel(const T* __restri
     if (ep[k] >= 0) partial[(int64_t)blockIdx.x * f * f + tid + 256 * k] = acc[k];
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void als_gram_sum_kernel(const T* __restrict__ partial, int64_t ranges, int ff,
-                                                           T* __restrict__ gram) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= ff) return;
-  T s = (T)0;
-  if (ranges > 0) s = partial[e];
-  for (int64_t r = 1; r < ranges; ++r) s = s + partial[r * ff + e];
-  gram[e] = s;
-}
-
 __global__ void als_info_kernel(const int* __restrict__ lowest, int* __restrict__ info) {
   const int v = *lowest;
   if (v != 0) atomicCAS(info, 0, 1 + (0x7fffffff - v));
 }
-
-size_t als_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 size_t als_lds_bytes(int f, int B, size_t elem) {
   const int nb = (f + B - 1) / B, fp = nb * B;
@@ -307,16 +280,14 @@ int als_run(const T* R, int64_t ldr, int64_t m, int64_t n, const T* Y, int64_t l
   T* gram = nullptr;
   if (implicit) {
     gram = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(ws) + FLAG_BYTES);
-    T* partial = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(gram) + als_align((size_t)f * f * sizeof(T)));
+    T* partial = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(gram) + sp_align256((size_t)f * f * sizeof(T)));
     const int64_t len = gram_range_len(n), ranges = (n + len - 1) / len;
     if (ranges > 0) {
       hipLaunchKernelGGL(als_gram_partial_kernel<T>, dim3((unsigned)ranges), dim3(256), 0, st, Y, ldy, n, (int)f, len,
                          partial);
       SP_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(als_gram_sum_kernel<T>, dim3((unsigned)((f * f + 255) / 256)), dim3(256), 0, st, partial, ranges,
-                       (int)(f * f), gram);
-    SP_CHECK_LAUNCH();
+    if (sp_partial_sum<T>(partial, ranges, f, f, gram, f, (const T*)nullptr, 0, (T*)nullptr, st)) return 1;
   }
   const unsigned blocks = (unsigned)((m + ROWS - 1) / ROWS);
   if (f <= SMALL_F) {
@@ -349,27 +320,25 @@ extern "C" size_t sp_als_solve_workspace_bytes(int32_t dtype, int64_t m, int64_t
   if (!als_args_ok(dtype, m, n, f)) return 0;
   if (!implicit) return FLAG_BYTES;
   const int64_t len = gram_range_len(n), ranges = (n + len - 1) / len;
-  const size_t sq = als_align((size_t)f * f * sp_dtype_size(dtype));
+  const size_t sq = sp_align256((size_t)f * f * sp_dtype_size(dtype));
   return FLAG_BYTES + sq + (size_t)(ranges > 0 ? ranges : 1) * sq;
 }
 
 extern "C" int sp_als_solve(int32_t dtype, const void* d_R, int64_t ldr, int64_t m, int64_t n, const void* d_Y,
                             int64_t ldy, int32_t f, double la, double alpha, int32_t implicit, void* d_X, int64_t ldx,
                             int32_t* d_info, void* d_ws, size_t ws_bytes, void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64) SP_FAIL("sp_als_solve: dtype must be f32 or f64; convert with astype first");
-  if (f < 1 || f > SP_ALS_MAX_F) SP_FAIL("sp_als_solve: f = %d is outside 1 .. %d", (int)f, SP_ALS_MAX_F);
-  if (m < 0 || n < 0 || ldr < n || ldy < f || ldx < f)
-    SP_FAIL("sp_als_solve: bad shape m=%lld n=%lld f=%d ldr=%lld ldy=%lld ldx=%lld", (long long)m, (long long)n, (int)f,
-            (long long)ldr, (long long)ldy, (long long)ldx);
-  if (m > 0x7ffffffeLL) SP_FAIL("sp_als_solve: %lld rows in one call (at most 2^31 - 2)", (long long)m);
-  if (m == 0) return 0;
-  const size_t need = sp_als_solve_workspace_bytes(dtype, m, n, f, implicit);
-  if (!d_info || !d_ws || ws_bytes < need) SP_FAIL("sp_als_solve: info word or workspace missing (%zu bytes, %zu needed)",
-                                                   ws_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SP_F32)
-    return als_run<float>((const float*)d_R, ldr, m, n, (const float*)d_Y, ldy, f, la, alpha, implicit, (float*)d_X, ldx,
-                          d_info, d_ws, st);
-  return als_run<double>((const double*)d_R, ldr, m, n, (const double*)d_Y, ldy, f, la, alpha, implicit, (double*)d_X,
-                         ldx, d_info, d_ws, st);
+  return sp_float_dispatch("sp_als_solve", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (f < 1 || f > SP_ALS_MAX_F) SP_FAIL("sp_als_solve: f = %d is outside 1 .. %d", (int)f, SP_ALS_MAX_F);
+    if (m < 0 || n < 0 || ldr < n || ldy < f || ldx < f)
+      SP_FAIL("sp_als_solve: bad shape m=%lld n=%lld f=%d ldr=%lld ldy=%lld ldx=%lld", (long long)m, (long long)n, (int)f,
+              (long long)ldr, (long long)ldy, (long long)ldx);
+    if (m > 0x7ffffffeLL) SP_FAIL("sp_als_solve: %lld rows in one call (at most 2^31 - 2)", (long long)m);
+    if (m == 0) return 0;
+    const size_t need = sp_als_solve_workspace_bytes(dtype, m, n, f, implicit);
+    if (!d_info || !d_ws || ws_bytes < need) SP_FAIL("sp_als_solve: info word or workspace missing (%zu bytes, %zu needed)",
+                                                     ws_bytes, need);
+    return als_run<T>((const T*)d_R, ldr, m, n, (const T*)d_Y, ldy, f, la, alpha, implicit, (T*)d_X, ldx, d_info, d_ws,
+                      (hipStream_t)stream);
+  });
 }

@@ -19,18 +19,13 @@
 // Everything in one block of (x) is padded with +inf in LDS where the matrix ends; stores are guarded.
 #include <limits>
 
-#include "sp_common.hpp"
+#include "sp_extras_common.hpp"
 #include "../../include/spartan_hip_graph.h"
 
 namespace {
 
 constexpr int BS = 64;        // block size
 constexpr int PITCH = 68;     // elements between the rows of a staged block (BS + 4: 16-byte aligned rows)
-
-template <typename T>
-struct alignas(16) Vec4 {
-  T v[4];
-};
 
 template <typename T>
 __device__ __forceinline__ T inf_of() {
@@ -310,27 +305,27 @@ int graph_run(const T* dist, const int64_t* idx, int64_t ldk, int64_t n, int64_t
 }  // namespace
 
 extern "C" int sp_apsp(int32_t dtype, void* d_D, int64_t ldd, int64_t n, int32_t* d_info, void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64) SP_FAIL("sp_apsp: dtype must be f32 or f64; convert with astype first");
-  if (n < 0 || ldd < n) SP_FAIL("sp_apsp: bad shape n=%lld ldd=%lld", (long long)n, (long long)ldd);
-  if (n > 65535LL * BS) SP_FAIL("sp_apsp: order %lld is too large (at most %lld)", (long long)n, 65535LL * BS);
-  if (!d_info) SP_FAIL("sp_apsp: NULL info");
-  hipStream_t st = (hipStream_t)stream;
-  SP_HIP(hipMemsetAsync(d_info, 0, sizeof(int32_t), st));
-  if (n == 0) return 0;
-  if (dtype == SP_F32) return apsp_run<float>((float*)d_D, ldd, n, d_info, st);
-  return apsp_run<double>((double*)d_D, ldd, n, d_info, st);
+  return sp_float_dispatch("sp_apsp", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (n < 0 || ldd < n) SP_FAIL("sp_apsp: bad shape n=%lld ldd=%lld", (long long)n, (long long)ldd);
+    if (n > 65535LL * BS) SP_FAIL("sp_apsp: order %lld is too large (at most %lld)", (long long)n, 65535LL * BS);
+    if (!d_info) SP_FAIL("sp_apsp: NULL info");
+    hipStream_t st = (hipStream_t)stream;
+    SP_HIP(hipMemsetAsync(d_info, 0, sizeof(int32_t), st));
+    if (n == 0) return 0;
+    return apsp_run<T>((T*)d_D, ldd, n, d_info, st);
+  });
 }
 
 extern "C" int sp_graph_from_knn(int32_t dtype, const void* d_dist, const int64_t* d_idx, int64_t ldk, int64_t n,
                                  int64_t k, void* d_W, int64_t ldw, void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64) SP_FAIL("sp_graph_from_knn: dtype must be f32 or f64; convert with astype first");
-  if (n < 0 || k < 0 || ldk < k || ldw < n)
-    SP_FAIL("sp_graph_from_knn: bad shape n=%lld k=%lld ldk=%lld ldw=%lld", (long long)n, (long long)k, (long long)ldk,
-            (long long)ldw);
-  if (n > 0x7fffffffLL / 2) SP_FAIL("sp_graph_from_knn: order %lld is too large", (long long)n);
-  if (n == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SP_F32)
-    return graph_run<float>((const float*)d_dist, d_idx, ldk, n, k, (float*)d_W, ldw, st);
-  return graph_run<double>((const double*)d_dist, d_idx, ldk, n, k, (double*)d_W, ldw, st);
+  return sp_float_dispatch("sp_graph_from_knn", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (n < 0 || k < 0 || ldk < k || ldw < n)
+      SP_FAIL("sp_graph_from_knn: bad shape n=%lld k=%lld ldk=%lld ldw=%lld", (long long)n, (long long)k, (long long)ldk,
+              (long long)ldw);
+    if (n > 0x7fffffffLL / 2) SP_FAIL("sp_graph_from_knn: order %lld is too large", (long long)n);
+    if (n == 0) return 0;
+    return graph_run<T>((const T*)d_dist, d_idx, ldk, n, k, (T*)d_W, ldw, (hipStream_t)stream);
+  });
 }

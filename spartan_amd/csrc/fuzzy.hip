@@ -2,23 +2,24 @@
 //   spartan/examples/fuzzy_kmeans.py   kmeans_map2_dist_mapper   (:41-50: cdist, ** 1 / (m - 1), row-normalise)
 //                                      kmeans_map2_center_mapper (:53-62: dot(X.T, fuzzy ** m))
 // The contract is in include/spartan_hip_fuzzy.h.  Three kernels:
-//   fuzzy_norm_kernel        a workgroup of 256 threads = 64 rows x all centres.  The distance tile is sp_knn's
-//                            (knn_scan_kernel): centres pass through LDS 64 at a time, both operands in chunks of 16
-//                            features stored feature-major with a row pitch of 68, the next chunk in flight in
-//                            registers; thread (ty, tx) of the 16 x 16 grid holds the 4 x 4 values of d2 of rows
-//                            4 ty .. 4 ty + 3 and centres 4 tx .. 4 tx + 3, each ONE accumulator.  The 16 lanes that
-//                            share a row are neighbours in a wave: the row's arg-max of d2 and its sum of p are
-//                            butterflies over those lanes (the order is in the header), no LDS and no barrier.
+//   fuzzy_norm_kernel        a workgroup of 256 threads = 64 rows x all centres.  The distance tile is the one sp_knn
+//                            uses (sp_d2_tile, sp_extras_common.hpp): centres pass through LDS 64 at a time, both
+//                            operands in chunks of 16 features stored feature-major with a row pitch of 68, the next
+//                            chunk in flight in registers; thread (ty, tx) of the 16 x 16 grid holds the 4 x 4 values of
+//                            d2 of rows 4 ty .. 4 ty + 3 and centres 4 tx .. 4 tx + 3, each ONE accumulator.  The 16
+//                            lanes that share a row are neighbours in a wave: the row's arg-max of d2 and its sum of p
+//                            are butterflies over those lanes (the order is in the header), no LDS and no barrier.
 //   fuzzy_accumulate_kernel  a workgroup = 64 centres x a panel of 128 features x a range of row blocks.  Per block of
 //                            64 rows: the same distance tile, w = (p / z)^m into LDS [row][centre], the rows' panel of
 //                            X into LDS [row][feature], then 64 steps r = 0 .. 63 in which thread (tf, tc) adds
 //                            w[r][4 tc ..] x[r][8 tf ..] onto its 4 x 8 sums (two aligned 16-byte reads of w and x for
 //                            32 multiply-adds); the threads of tf = 0 carry wsum of their centres.
-//   fuzzy_combine_kernel     the ranges' partials, added in ascending order.
+//   sp_partial_sum_kernel    the ranges' partials, added in ascending order: the k x d sums and the k weights behind
+//                            them in one launch (sp_extras_common.hpp).
 #include <cmath>
 #include <limits>
 
-#include "sp_common.hpp"
+#include "sp_extras_common.hpp"
 #include "../../include/spartan_hip_fuzzy.h"
 
 namespace {
@@ -26,21 +27,11 @@ namespace {
 constexpr int RB = SP_FUZZY_ROWS;      // rows per workgroup
 constexpr int CB = SP_FUZZY_CENTERS;   // centres per pass
 constexpr int FP = SP_FUZZY_PANEL;     // features per panel of the accumulation
-constexpr int DC = 16;                 // features per chunk
-constexpr int PITCH = 68;              // elements between the feature rows of a staged chunk (RB + 4: 16-byte aligned rows)
+constexpr int DC = SP_D2_DC;           // features per chunk of the distance tile
+constexpr int PITCH = SP_D2_PITCH;     // elements between the feature rows of a staged chunk
 constexpr int WP = CB + 4;             // elements between the rows of the staged weights
 constexpr int XP = FP + 4;             // elements between the rows of the staged panel
 static_assert(RB == 64 && CB == 64 && FP == 128, "the thread maps below are written for 64 x 64 x 128");
-
-template <typename T>
-struct alignas(16) Vec4 {
-  T v[4];
-};
-
-__device__ __forceinline__ float sqrt_t(float a) { return __builtin_sqrtf(a); }
-__device__ __forceinline__ double sqrt_t(double a) { return __builtin_sqrt(a); }
-__device__ __forceinline__ float pow_t(float a, float b) { return powf(a, b); }
-__device__ __forceinline__ double pow_t(double a, double b) { return pow(a, b); }
 
 // the scalars of a call, each rounded to T once on the host
 template <typename T>
@@ -72,70 +63,6 @@ __device__ __forceinline__ bool beats(T a, int64_t ia, T b, int64_t ib) {
   return a > b || (a == b && ia < ib);
 }
 
-// acc[a][b] <- d2 of row r0 + 4 ty + a and centre c0 + 4 tx + b: sp_knn's tile, word for word.  Rows >= n, centres
-// >= k and features >= d load 0.  Every thread of the workgroup calls it (it synchronises the workgroup).
-template <typename T>
-__device__ __forceinline__ void d2_tile(const T* __restrict__ X, int64_t ldx, int64_t n, int64_t r0,
-                                        const T* __restrict__ C, int64_t ldc, int64_t k, int64_t c0, int64_t d, T* xs,
-                                        T* cs, int tid, T (&acc)[4][4]) {
-  const int ty = tid >> 4, tx = tid & 15;
-  const int lj = tid & 15, lr0 = tid >> 4;
-  const int64_t nchunks = (d + DC - 1) / DC;
-  T xn[4], cn[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = (T)0;
-
-  auto fetch = [&](int64_t c) {
-    const int64_t col = c * DC + lj;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t xr = r0 + lr0 + 16 * i, cr = c0 + lr0 + 16 * i;
-      xn[i] = (col < d && xr < n) ? X[xr * ldx + col] : (T)0;
-      cn[i] = (col < d && cr < k) ? C[cr * ldc + col] : (T)0;
-    }
-  };
-  if (nchunks > 0) fetch(0);
-  for (int64_t c = 0; c < nchunks; ++c) {
-    __syncthreads();                    // the previous chunk has been read by everyone
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      xs[lj * PITCH + lr0 + 16 * i] = xn[i];
-      cs[lj * PITCH + lr0 + 16 * i] = cn[i];
-    }
-    __syncthreads();
-    if (c + 1 < nchunks) fetch(c + 1);
-    const int jn = (int)((d - c * DC) < DC ? (d - c * DC) : DC);
-    if (jn == DC) {
-#pragma unroll 4
-      for (int j = 0; j < DC; ++j) {
-        const Vec4<T> xv = *reinterpret_cast<const Vec4<T>*>(xs + j * PITCH + ty * 4);
-        const Vec4<T> cv = *reinterpret_cast<const Vec4<T>*>(cs + j * PITCH + tx * 4);
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const T t = xv.v[a] - cv.v[b];
-            acc[a][b] = acc[a][b] + t * t;
-          }
-      }
-    } else {
-      for (int j = 0; j < jn; ++j) {
-        const Vec4<T> xv = *reinterpret_cast<const Vec4<T>*>(xs + j * PITCH + ty * 4);
-        const Vec4<T> cv = *reinterpret_cast<const Vec4<T>*>(cs + j * PITCH + tx * 4);
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const T t = xv.v[a] - cv.v[b];
-            acc[a][b] = acc[a][b] + t * t;
-          }
-      }
-    }
-  }
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void fuzzy_norm_kernel(const T* __restrict__ X, int64_t ldx, int64_t n,
                                                          const T* __restrict__ C, int64_t ldc, int64_t k, int64_t d,
@@ -157,7 +84,7 @@ __global__ __launch_bounds__(256) void fuzzy_norm_kernel(const T* __restrict__ X
 
   T acc[4][4];
   for (int64_t c0 = 0; c0 < k; c0 += CB) {
-    d2_tile<T>(X, ldx, n, r0, C, ldc, k, c0, d, xs, cs, tid, acc);
+    sp_d2_tile<T>(X, ldx, n, r0, C, ldc, k, c0, d, xs, cs, tid, acc);
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       T g = (T)0, v = (T)-1;
@@ -205,7 +132,7 @@ __global__ __launch_bounds__(256) void fuzzy_norm_kernel(const T* __restrict__ X
 
   if (U) {
     for (int64_t c0 = 0; c0 < k; c0 += CB) {
-      d2_tile<T>(X, ldx, n, r0, C, ldc, k, c0, d, xs, cs, tid, acc);
+      sp_d2_tile<T>(X, ldx, n, r0, C, ldc, k, c0, d, xs, cs, tid, acc);
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
         const int64_t row = r0 + ty * 4 + a;
@@ -252,7 +179,7 @@ __global__ __launch_bounds__(256) void fuzzy_accumulate_kernel(const T* __restri
   T acc[4][4];
   for (int64_t rb = rb_b; rb < rb_e; ++rb) {
     const int64_t r0 = rb * RB;
-    d2_tile<T>(X, ldx, n, r0, C, ldc, k, c0, d, xs, cs, tid, acc);
+    sp_d2_tile<T>(X, ldx, n, r0, C, ldc, k, c0, d, xs, cs, tid, acc);
     __syncthreads();                    // the previous block's weights and panel have been read by everyone
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
@@ -306,26 +233,6 @@ __global__ __launch_bounds__(256) void fuzzy_accumulate_kernel(const T* __restri
   }
 }
 
-// S[j, f] <- P_0[j, f] + P_1[j, f] + ... in ascending order; the same for the k weights behind the k * d sums
-template <typename T>
-__global__ __launch_bounds__(256) void fuzzy_combine_kernel(const T* __restrict__ Ps, const T* __restrict__ Pw,
-                                                            int64_t ranges, int64_t k, int64_t d, T* __restrict__ S,
-                                                            int64_t lds, T* __restrict__ W) {
-  const int64_t kd = k * d, total = kd + k;
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-    if (idx < kd) {
-      T a = Ps[idx];
-      for (int64_t g = 1; g < ranges; ++g) a = a + Ps[g * kd + idx];
-      S[(idx / d) * lds + idx % d] = a;
-    } else {
-      const int64_t j = idx - kd;
-      T a = Pw[j];
-      for (int64_t g = 1; g < ranges; ++g) a = a + Pw[g * k + j];
-      W[j] = a;
-    }
-  }
-}
-
 int64_t fz_cblocks(int64_t k) { return (k + CB - 1) / CB; }
 int64_t fz_panels(int64_t d) { return d > 0 ? (d + FP - 1) / FP : 1; }      // (d = 0: one panel, for wsum)
 
@@ -343,24 +250,35 @@ int64_t fz_ranges(int64_t n, int64_t k, int64_t d, int32_t splits) {
   return want < 1 ? 1 : want;
 }
 
-size_t fz_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// the workspace: z (a value per row), then with more than one range their partial sums and partial weights
+struct Layout {
+  int64_t ranges;
+  size_t z_bytes, s_bytes, w_bytes;
+  size_t total() const { return z_bytes + s_bytes + w_bytes; }
+};
+
+Layout fz_layout(size_t sz, int64_t n, int64_t k, int64_t d, int32_t splits) {
+  Layout l;
+  l.ranges = fz_ranges(n, k, d, splits);
+  l.z_bytes = sp_align256((size_t)(n > 0 ? n : 1) * sz);
+  l.s_bytes = l.ranges > 1 ? sp_align256((size_t)l.ranges * k * d * sz) : 0;
+  l.w_bytes = l.ranges > 1 ? (size_t)l.ranges * k * sz : 0;
+  return l;
+}
 
 template <typename T>
 int fz_run(const T* X, int64_t ldx, int64_t n, const T* C, int64_t ldc, int64_t k, int64_t d, double m, int32_t splits,
            int64_t* labels, T* S, int64_t lds, T* W, T* U, int64_t ldu, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int64_t ranges = fz_ranges(n, k, d, splits);
-  const int64_t cblocks = fz_cblocks(k), panels = fz_panels(d), nb = (n + RB - 1) / RB;
-  const size_t zbytes = fz_align((size_t)(n > 0 ? n : 1) * sizeof(T));
-  const size_t sbytes = ranges > 1 ? fz_align((size_t)ranges * k * d * sizeof(T)) : 0;
-  const size_t need = zbytes + sbytes + (ranges > 1 ? (size_t)ranges * k * sizeof(T) : 0);
-  if (!ws || ws_bytes < need) SP_FAIL("sp_fuzzy_step: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  const Layout l = fz_layout(sizeof(T), n, k, d, splits);
+  const int64_t ranges = l.ranges, cblocks = fz_cblocks(k), panels = fz_panels(d), nb = (n + RB - 1) / RB;
+  if (!ws || ws_bytes < l.total()) SP_FAIL("sp_fuzzy_step: workspace of %zu bytes, %zu needed", ws_bytes, l.total());
   if (nb > 0x7fffffffLL || (double)cblocks * (double)panels * (double)ranges > 2147483647.0)
     SP_FAIL("sp_fuzzy_step: n=%lld k=%lld d=%lld are too many workgroups for one launch", (long long)n, (long long)k,
             (long long)d);
   unsigned char* wsb = reinterpret_cast<unsigned char*>(ws);
   T* z = reinterpret_cast<T*>(wsb);
-  T* ps = reinterpret_cast<T*>(wsb + zbytes);
-  T* pw = reinterpret_cast<T*>(wsb + zbytes + sbytes);
+  T* ps = reinterpret_cast<T*>(wsb + l.z_bytes);
+  T* pw = reinterpret_cast<T*>(wsb + l.z_bytes + l.s_bytes);
 
   Scalars<T> sc;
   sc.e = (T)(1.0 / (m - 1.0));
@@ -383,12 +301,8 @@ int fz_run(const T* X, int64_t ldx, int64_t n, const T* C, int64_t ldc, int64_t 
     hipLaunchKernelGGL(fuzzy_accumulate_kernel<T>, dim3((unsigned)(cblocks * panels)), dim3(256), smem, st, X, ldx, n, C,
                        ldc, k, d, sc, z, cblocks, panels, (int64_t)1, S, lds, (int64_t)0, W, (int64_t)0);
   SP_CHECK_LAUNCH();
-  if (ranges > 1) {
-    int64_t blocks = (k * d + k + 255) / 256;
-    if (blocks > SP_CUS * SP_BLOCKS_PER_CU) blocks = SP_CUS * SP_BLOCKS_PER_CU;
-    hipLaunchKernelGGL(fuzzy_combine_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, ps, pw, ranges, k, d, S, lds, W);
-    SP_CHECK_LAUNCH();
-  }
+  // S[j, f] <- P_0[j, f] + P_1[j, f] + ... in ascending order; the same for the k weights behind the k * d sums
+  if (ranges > 1) return sp_partial_sum<T>(ps, ranges, k, d, S, lds, pw, k, W, st);
   return 0;
 }
 
@@ -398,29 +312,23 @@ bool fz_shape_ok(int64_t n, int64_t k, int64_t d, int32_t splits) { return n >= 
 
 extern "C" size_t sp_fuzzy_step_workspace_bytes(int32_t dtype, int64_t n, int64_t k, int64_t d, int32_t splits) {
   if ((dtype != SP_F32 && dtype != SP_F64) || !fz_shape_ok(n, k, d, splits)) return 0;
-  const size_t sz = sp_dtype_size(dtype);
-  const int64_t ranges = fz_ranges(n, k, d, splits);
-  size_t need = fz_align((size_t)(n > 0 ? n : 1) * sz);
-  if (ranges > 1) need += fz_align((size_t)ranges * k * d * sz) + (size_t)ranges * k * sz;
-  return need;
+  return fz_layout(sp_dtype_size(dtype), n, k, d, splits).total();
 }
 
 extern "C" int sp_fuzzy_step(int32_t dtype, const void* d_X, int64_t ldx, int64_t n, const void* d_C, int64_t ldc,
                              int64_t k, int64_t d, double m, int32_t splits, int64_t* d_labels, void* d_sums,
                              int64_t lds, void* d_wsum, void* d_U, int64_t ldu, void* d_ws, size_t ws_bytes,
                              void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64) SP_FAIL("sp_fuzzy_step: dtype must be f32 or f64; convert with astype first");
-  if (!(m > 1.0) || std::isinf(m)) SP_FAIL("sp_fuzzy_step: m = %g must be finite and > 1", m);
-  if (k < 1) SP_FAIL("sp_fuzzy_step: k = %lld must be at least 1", (long long)k);
-  if (!fz_shape_ok(n, k, d, splits) || ldx < d || ldc < d || lds < d || (d_U && ldu < k))
-    SP_FAIL("sp_fuzzy_step: bad shape n=%lld k=%lld d=%lld ldx=%lld ldc=%lld lds=%lld ldu=%lld splits=%d", (long long)n,
-            (long long)k, (long long)d, (long long)ldx, (long long)ldc, (long long)lds, (long long)ldu, (int)splits);
-  if (!d_wsum || (!d_sums && d > 0)) SP_FAIL("sp_fuzzy_step: sums and wsum are required");
-  if (n > 0 && d > 0 && (!d_X || !d_C)) SP_FAIL("sp_fuzzy_step: X and C are required");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SP_F32)
-    return fz_run<float>((const float*)d_X, ldx, n, (const float*)d_C, ldc, k, d, m, splits, d_labels, (float*)d_sums,
-                         lds, (float*)d_wsum, (float*)d_U, ldu, d_ws, ws_bytes, st);
-  return fz_run<double>((const double*)d_X, ldx, n, (const double*)d_C, ldc, k, d, m, splits, d_labels, (double*)d_sums,
-                        lds, (double*)d_wsum, (double*)d_U, ldu, d_ws, ws_bytes, st);
+  return sp_float_dispatch("sp_fuzzy_step", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (!(m > 1.0) || std::isinf(m)) SP_FAIL("sp_fuzzy_step: m = %g must be finite and > 1", m);
+    if (k < 1) SP_FAIL("sp_fuzzy_step: k = %lld must be at least 1", (long long)k);
+    if (!fz_shape_ok(n, k, d, splits) || ldx < d || ldc < d || lds < d || (d_U && ldu < k))
+      SP_FAIL("sp_fuzzy_step: bad shape n=%lld k=%lld d=%lld ldx=%lld ldc=%lld lds=%lld ldu=%lld splits=%d", (long long)n,
+              (long long)k, (long long)d, (long long)ldx, (long long)ldc, (long long)lds, (long long)ldu, (int)splits);
+    if (!d_wsum || (!d_sums && d > 0)) SP_FAIL("sp_fuzzy_step: sums and wsum are required");
+    if (n > 0 && d > 0 && (!d_X || !d_C)) SP_FAIL("sp_fuzzy_step: X and C are required");
+    return fz_run<T>((const T*)d_X, ldx, n, (const T*)d_C, ldc, k, d, m, splits, d_labels, (T*)d_sums, lds, (T*)d_wsum,
+                     (T*)d_U, ldu, d_ws, ws_bytes, (hipStream_t)stream);
+  });
 }

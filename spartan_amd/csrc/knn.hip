@@ -6,7 +6,8 @@
 //   knn_scan_kernel   a workgroup of 256 threads = 64 queries x one range of the points.  Points pass through LDS 64 at
 //                     a time, both operands in chunks of 16 features stored feature-major with a row pitch of 68 (reads
 //                     are 16-byte, 16-byte aligned; the next chunk is in flight in registers while this one is
-//                     used).  Thread (ty, tx) of the 16 x 16 grid holds the 4 x 4 distances of queries 4 ty .. 4 ty + 3
+//                     used): sp_d2_tile of sp_extras_common.hpp, written out in this kernel (the comment there says
+//                     why).  Thread (ty, tx) of the 16 x 16 grid holds the 4 x 4 distances of queries 4 ty .. 4 ty + 3
 //                     and points 4 tx .. 4 tx + 3; every one is ONE accumulator that takes (q_j - x_j)^2 for j = 0, 1, ...
 //                     in turn.  Wave w therefore holds queries 16 w .. 16 w + 15 and nobody else does: their candidate
 //                     lists (LDS, sorted by (d2, index), k entries each) are private to the wave and selection needs
@@ -19,25 +20,15 @@
 // list is full (about k ln(n / k) per query over n points).
 #include <limits>
 
-#include "sp_common.hpp"
+#include "sp_extras_common.hpp"
 #include "../../include/spartan_hip_knn.h"
 
 namespace {
 
 constexpr int QB = 64;        // queries per workgroup
 constexpr int PB = 64;        // points per pass
-constexpr int DC = 16;        // features per chunk
-constexpr int PITCH = 68;     // elements between the feature rows of a staged chunk (QB + 4: 16-byte aligned rows)
-
-template <typename T>
-struct alignas(16) Vec4 {
-  T v[4];
-};
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
+constexpr int DC = SP_D2_DC;        // features per chunk of the distance tile
+constexpr int PITCH = SP_D2_PITCH;  // elements between the feature rows of a staged chunk
 
 // the total order on (d2, index); false whenever a is NaN
 template <typename T, typename I>
@@ -63,11 +54,11 @@ __device__ __forceinline__ void list_insert(T* ld, I* li, int k, int lane, T dv,
   if (h1) { d1 = ld[lane + 64]; i1 = li[lane + 64]; }
   const bool lt0 = h0 && key_less(d0, i0, dv, iv), lt1 = h1 && key_less(d1, i1, dv, iv);
   const int p = __popcll(__ballot(lt0)) + __popcll(__ballot(lt1));     // entries below the new key: its position
-  wave_sync();                                                         // (every read above before any write below)
+  sp_wave_sync();                                                      // (every read above before any write below)
   if (h0 && !lt0 && lane + 1 < k) { ld[lane + 1] = d0; li[lane + 1] = i0; }
   if (h1 && !lt1 && lane + 65 < k) { ld[lane + 65] = d1; li[lane + 65] = i1; }
   if (lane == 0 && p < k) { ld[p] = dv; li[p] = iv; }
-  wave_sync();
+  sp_wave_sync();
 }
 
 template <typename T>
@@ -89,8 +80,12 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(const T* __restrict__ Q, 
   const int64_t pb = (int64_t)split * np / splits, pe = (int64_t)(split + 1) * np / splits;
 
   list_clear(cd + (size_t)wave * 16 * k, ci + (size_t)wave * 16 * k, 16 * k, lane);
-  wave_sync();
+  sp_wave_sync();
 
+  // The distance tile below is sp_d2_tile (sp_extras_common.hpp) written out: the same staging, the same order of
+  // accumulation, with `pe`, the range's end, in the place of its k.  A deliberate copy: called as a function the tile
+  // costs this kernel 12 VGPRs in fp64 and 1 - 4 % of its time (fp64; up to 2 % in fp32 at d = 16), measured in
+  // profiles/extras_shared_pieces_notes.md.  A change to either copy belongs in both.
   // staging: thread (lr0 + 16 i, lj), i = 0 .. 3, of the [64 rows][16 features] chunk: a row's 16 features are one
   // 64- or 128-byte run for 16 consecutive lanes
   const int lj = tid & 15, lr0 = tid >> 4;
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(const T* __restrict__ Q, 
     }
   }
 
-  wave_sync();
+  sp_wave_sync();
   for (int r = 0; r < 16; ++r) {
     const int row = wave * 16 + r;
     if (q0 + row >= nq) break;
@@ -203,7 +198,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const T* __restrict__ ca
   T* ld = ld_all[wave];
   int64_t* li = li_all[wave];
   list_clear(ld, li, k, lane);
-  wave_sync();
+  sp_wave_sync();
   const T* rd = cand_d + row * ldc;
   const int64_t* ri = cand_i + row * ldc;
   for (int64_t base = 0; base < m; base += 64) {
@@ -221,7 +216,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const T* __restrict__ ca
       if (key_less(dv, iv, ld[k - 1], li[k - 1])) list_insert(ld, li, k, lane, dv, iv);
     }
   }
-  wave_sync();
+  sp_wave_sync();
   for (int e = lane; e < k; e += 64) {
     const int64_t i = li[e];
     out_d[row * k + e] = ld[e];
@@ -244,7 +239,20 @@ int64_t knn_ranges(int64_t nq, int64_t np, int32_t k, int32_t splits) {
   return want < 1 ? 1 : want;
 }
 
-size_t knn_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// the workspace: with more than one range, every range's k candidates per query -- distances, then indices
+struct Layout {
+  int64_t ranges;
+  size_t d_bytes, i_bytes;
+  size_t total() const { return d_bytes + i_bytes; }
+};
+
+Layout knn_layout(size_t sz, int64_t nq, int64_t np, int32_t k, int32_t splits) {
+  Layout l;
+  l.ranges = knn_ranges(nq, np, k, splits);
+  l.d_bytes = l.ranges > 1 ? sp_align256((size_t)nq * l.ranges * k * sz) : 0;
+  l.i_bytes = l.ranges > 1 ? (size_t)nq * l.ranges * k * sizeof(int64_t) : 0;
+  return l;
+}
 
 template <typename T>
 int knn_merge_launch(const T* cd, const int64_t* ci, int64_t ldc, int64_t nq, int64_t m, int32_t k, T* od, int64_t* oi,
@@ -259,19 +267,17 @@ int knn_merge_launch(const T* cd, const int64_t* ci, int64_t ldc, int64_t nq, in
 template <typename T>
 int knn_run(const T* Q, int64_t ldq, int64_t nq, const T* X, int64_t ldx, int64_t np, int64_t d, int32_t k,
             int64_t index_offset, int32_t splits, T* od, int64_t* oi, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int64_t ranges = knn_ranges(nq, np, k, splits);
-  const int64_t qblocks = (nq + QB - 1) / QB;
+  const Layout l = knn_layout(sizeof(T), nq, np, k, splits);
+  const int64_t ranges = l.ranges, qblocks = (nq + QB - 1) / QB;
   if (qblocks * ranges > 0x7fffffffLL) SP_FAIL("sp_knn: %lld queries x %lld ranges are too many for one launch",
                                                (long long)nq, (long long)ranges);
   T* sd = od;
   int64_t* si = oi;
   int64_t ldo = k;
   if (ranges > 1) {
-    const size_t dbytes = knn_align((size_t)nq * ranges * k * sizeof(T));
-    const size_t need = dbytes + (size_t)nq * ranges * k * sizeof(int64_t);
-    if (!ws || ws_bytes < need) SP_FAIL("sp_knn: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    if (!ws || ws_bytes < l.total()) SP_FAIL("sp_knn: workspace of %zu bytes, %zu needed", ws_bytes, l.total());
     sd = reinterpret_cast<T*>(ws);
-    si = reinterpret_cast<int64_t*>(reinterpret_cast<unsigned char*>(ws) + dbytes);
+    si = reinterpret_cast<int64_t*>(reinterpret_cast<unsigned char*>(ws) + l.d_bytes);
     ldo = ranges * k;
   }
   const size_t lds = 2 * DC * PITCH * sizeof(T) + (size_t)QB * k * (sizeof(T) + sizeof(int32_t));
@@ -289,39 +295,34 @@ int knn_run(const T* Q, int64_t ldq, int64_t nq, const T* X, int64_t ldx, int64_
 extern "C" size_t sp_knn_workspace_bytes(int32_t dtype, int64_t nq, int64_t np, int64_t d, int32_t k, int32_t splits) {
   (void)d;
   if ((dtype != SP_F32 && dtype != SP_F64) || nq <= 0 || k < 1 || k > SP_KNN_MAX_K || splits < 0) return 0;
-  const int64_t ranges = knn_ranges(nq, np, k, splits);
-  if (ranges <= 1) return 0;
-  return knn_align((size_t)nq * ranges * k * sp_dtype_size(dtype)) + (size_t)nq * ranges * k * sizeof(int64_t);
+  return knn_layout(sp_dtype_size(dtype), nq, np, k, splits).total();
 }
 
 extern "C" int sp_knn(int32_t dtype, const void* d_Q, int64_t ldq, int64_t nq, const void* d_X, int64_t ldx, int64_t np,
                       int64_t d, int32_t k, int64_t index_offset, int32_t splits, void* d_dist2, int64_t* d_idx,
                       void* d_ws, size_t ws_bytes, void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64) SP_FAIL("sp_knn: dtype must be f32 or f64; convert with astype first");
-  if (k < 1 || k > SP_KNN_MAX_K) SP_FAIL("sp_knn: k = %d is outside 1 .. %d", (int)k, SP_KNN_MAX_K);
-  if (nq < 0 || np < 0 || d < 0 || ldq < d || ldx < d || splits < 0)
-    SP_FAIL("sp_knn: bad shape nq=%lld np=%lld d=%lld ldq=%lld ldx=%lld splits=%d", (long long)nq, (long long)np,
-            (long long)d, (long long)ldq, (long long)ldx, (int)splits);
-  if (np > 0x7ffffffeLL) SP_FAIL("sp_knn: %lld points in one call (at most 2^31 - 2; search tiles with index_offset "
-                                 "and merge)", (long long)np);
-  if (nq == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SP_F32)
-    return knn_run<float>((const float*)d_Q, ldq, nq, (const float*)d_X, ldx, np, d, k, index_offset, splits,
-                          (float*)d_dist2, d_idx, d_ws, ws_bytes, st);
-  return knn_run<double>((const double*)d_Q, ldq, nq, (const double*)d_X, ldx, np, d, k, index_offset, splits,
-                         (double*)d_dist2, d_idx, d_ws, ws_bytes, st);
+  return sp_float_dispatch("sp_knn", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (k < 1 || k > SP_KNN_MAX_K) SP_FAIL("sp_knn: k = %d is outside 1 .. %d", (int)k, SP_KNN_MAX_K);
+    if (nq < 0 || np < 0 || d < 0 || ldq < d || ldx < d || splits < 0)
+      SP_FAIL("sp_knn: bad shape nq=%lld np=%lld d=%lld ldq=%lld ldx=%lld splits=%d", (long long)nq, (long long)np,
+              (long long)d, (long long)ldq, (long long)ldx, (int)splits);
+    if (np > 0x7ffffffeLL) SP_FAIL("sp_knn: %lld points in one call (at most 2^31 - 2; search tiles with index_offset "
+                                   "and merge)", (long long)np);
+    if (nq == 0) return 0;
+    return knn_run<T>((const T*)d_Q, ldq, nq, (const T*)d_X, ldx, np, d, k, index_offset, splits, (T*)d_dist2, d_idx, d_ws,
+                      ws_bytes, (hipStream_t)stream);
+  });
 }
 
 extern "C" int sp_knn_merge(int32_t dtype, const void* d_cand_dist2, const int64_t* d_cand_idx, int64_t ldc, int64_t nq,
                             int64_t m, int32_t k, void* d_dist2, int64_t* d_idx, void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64) SP_FAIL("sp_knn_merge: dtype must be f32 or f64; convert with astype first");
-  if (k < 1 || k > SP_KNN_MAX_K) SP_FAIL("sp_knn_merge: k = %d is outside 1 .. %d", (int)k, SP_KNN_MAX_K);
-  if (nq < 0 || m < 0 || ldc < m) SP_FAIL("sp_knn_merge: bad shape nq=%lld m=%lld ldc=%lld", (long long)nq, (long long)m,
-                                          (long long)ldc);
-  if (nq == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SP_F32)
-    return knn_merge_launch<float>((const float*)d_cand_dist2, d_cand_idx, ldc, nq, m, k, (float*)d_dist2, d_idx, st);
-  return knn_merge_launch<double>((const double*)d_cand_dist2, d_cand_idx, ldc, nq, m, k, (double*)d_dist2, d_idx, st);
+  return sp_float_dispatch("sp_knn_merge", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (k < 1 || k > SP_KNN_MAX_K) SP_FAIL("sp_knn_merge: k = %d is outside 1 .. %d", (int)k, SP_KNN_MAX_K);
+    if (nq < 0 || m < 0 || ldc < m) SP_FAIL("sp_knn_merge: bad shape nq=%lld m=%lld ldc=%lld", (long long)nq, (long long)m,
+                                            (long long)ldc);
+    if (nq == 0) return 0;
+    return knn_merge_launch<T>((const T*)d_cand_dist2, d_cand_idx, ldc, nq, m, k, (T*)d_dist2, d_idx, (hipStream_t)stream);
+  });
 }

@@ -15,10 +15,11 @@
 //   lda_delta_kernel    a workgroup = 64 terms x a range of document blocks, its A block topic-major in LDS; per
 //                       sub-block of documents the stored B and X into LDS, the S tile, the signed quotient, and
 //                       acc[term][topic] += w b over the documents, a thread 4 terms x KT topics.
-//   lda_combine_kernel  the ranges' partials, added in ascending order (also the zero fill of D = 0).
+//   sp_partial_sum_kernel  the ranges' partials, added in ascending order (also the zero fill of D = 0;
+//                       sp_extras_common.hpp).
 #include <cmath>
 
-#include "sp_common.hpp"
+#include "sp_extras_common.hpp"
 #include "../../include/spartan_hip_lda.h"
 
 namespace {
@@ -36,14 +37,6 @@ struct Cfg {
   static constexpr int TC = (sizeof(T) == 8 || KT == 8) ? 32 : 64;
   static constexpr int DC = TC;
 };
-
-template <typename T, int N>
-struct alignas((sizeof(T) * N > 16 ? 16 : sizeof(T) * N)) VecN {
-  T v[N];
-};
-
-__device__ __forceinline__ float abs_t(float a) { return __builtin_fabsf(a); }
-__device__ __forceinline__ double abs_t(double a) { return __builtin_fabs(a); }
 
 // s[a][b] <- sum_t As[t][RA ty + a] Bs[t][RB tx + b], t = 0 .. kp - 1 ascending onto one accumulator that starts at 0
 template <typename T, int RA, int RB>
@@ -330,21 +323,6 @@ __global__ __launch_bounds__(256) void lda_delta_kernel(const T* __restrict__ X,
   }
 }
 
-// delta[t, j] <- P_0[t, j] + P_1[t, j] + ... in ascending order; 0 with no range at all (D = 0)
-template <typename T>
-__global__ __launch_bounds__(256) void lda_combine_kernel(const T* __restrict__ P, int64_t ranges, int64_t k, int64_t V,
-                                                          T* __restrict__ out, int64_t ldo) {
-  const int64_t kv = k * V;
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < kv; idx += (int64_t)gridDim.x * 256) {
-    T a = (T)0;
-    if (ranges > 0) {
-      a = P[idx];
-      for (int64_t g = 1; g < ranges; ++g) a = a + P[g * kv + idx];
-    }
-    out[(idx / V) * ldo + idx % V] = a;
-  }
-}
-
 int lda_kt(int64_t k) { return k <= 16 ? 1 : k <= 32 ? 2 : k <= 64 ? 4 : 8; }
 
 // the number of ranges the document blocks are cut into
@@ -361,8 +339,6 @@ int64_t lda_ranges(int64_t V, int64_t D, int64_t k, int32_t splits) {
   return want < 1 ? 1 : want;
 }
 
-size_t lda_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct Layout {
   size_t a_bytes, b_bytes, p_bytes;
   int64_t ranges;
@@ -373,9 +349,9 @@ Layout lda_layout(size_t sz, int64_t V, int64_t D, int64_t k, int32_t splits) {
   Layout l;
   const int64_t kp = 16 * lda_kt(k);
   l.ranges = lda_ranges(V, D, k, splits);
-  l.a_bytes = lda_align((size_t)(V > 0 ? V : 1) * kp * sz);
-  l.b_bytes = lda_align((size_t)(D > 0 ? D : 1) * kp * sz);
-  l.p_bytes = l.ranges > 1 ? lda_align((size_t)l.ranges * k * V * sz) : 0;
+  l.a_bytes = sp_align256((size_t)(V > 0 ? V : 1) * kp * sz);
+  l.b_bytes = sp_align256((size_t)(D > 0 ? D : 1) * kp * sz);
+  l.p_bytes = l.ranges > 1 ? sp_align256((size_t)l.ranges * k * V * sz) : 0;
   return l;
 }
 
@@ -410,13 +386,9 @@ int lda_launch(const T* X, int64_t ldx, int64_t V, int64_t D, const T* N, int64_
                          tblocks, (int64_t)1, delta, ldd, (int64_t)0);
     SP_CHECK_LAUNCH();
   }
-  if (D == 0 || ranges > 1) {
-    int64_t blocks = (k * V + 255) / 256;
-    if (blocks > SP_CUS * SP_BLOCKS_PER_CU) blocks = SP_CUS * SP_BLOCKS_PER_CU;
-    hipLaunchKernelGGL(lda_combine_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, P, D == 0 ? (int64_t)0 : ranges, k,
-                       V, delta, ldd);
-    SP_CHECK_LAUNCH();
-  }
+  // delta[t, j] <- P_0[t, j] + P_1[t, j] + ... in ascending order; 0 with no range at all (D = 0)
+  if (D == 0 || ranges > 1)
+    return sp_partial_sum<T>(P, D == 0 ? (int64_t)0 : ranges, k, V, delta, ldd, (const T*)nullptr, 0, (T*)nullptr, st);
   return 0;
 }
 
@@ -461,19 +433,17 @@ extern "C" int sp_lda_step(int32_t dtype, const void* d_X, int64_t ldx, int64_t 
                            int64_t ldn, int64_t k, double alpha, double eta, int32_t iters, int32_t splits,
                            void* d_delta, int64_t ldd, void* d_doc_topics, int64_t ldt, void* d_ws, size_t ws_bytes,
                            void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64) SP_FAIL("sp_lda_step: dtype must be f32 or f64; convert with astype first");
-  if (k < 1 || k > SP_LDA_MAX_K) SP_FAIL("sp_lda_step: k = %lld must be in 1 .. %d", (long long)k, SP_LDA_MAX_K);
-  if (iters < 1) SP_FAIL("sp_lda_step: iters = %d must be at least 1", (int)iters);
-  if (!(alpha > 0.0) || std::isinf(alpha)) SP_FAIL("sp_lda_step: alpha = %g must be finite and > 0", alpha);
-  if (!(eta > 0.0) || std::isinf(eta)) SP_FAIL("sp_lda_step: eta = %g must be finite and > 0", eta);
-  if (!lda_shape_ok(V, D, k, iters, splits) || ldx < D || ldn < V || (d_delta && ldd < V) || (d_doc_topics && ldt < k))
-    SP_FAIL("sp_lda_step: bad shape V=%lld D=%lld k=%lld ldx=%lld ldn=%lld ldd=%lld ldt=%lld splits=%d", (long long)V,
-            (long long)D, (long long)k, (long long)ldx, (long long)ldn, (long long)ldd, (long long)ldt, (int)splits);
-  if (V > 0 && (!d_N || (D > 0 && !d_X))) SP_FAIL("sp_lda_step: X and N are required");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SP_F32)
-    return lda_run<float>((const float*)d_X, ldx, V, D, (const float*)d_N, ldn, k, alpha, eta, iters, splits,
-                          (float*)d_delta, ldd, (float*)d_doc_topics, ldt, d_ws, ws_bytes, st);
-  return lda_run<double>((const double*)d_X, ldx, V, D, (const double*)d_N, ldn, k, alpha, eta, iters, splits,
-                         (double*)d_delta, ldd, (double*)d_doc_topics, ldt, d_ws, ws_bytes, st);
+  return sp_float_dispatch("sp_lda_step", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (k < 1 || k > SP_LDA_MAX_K) SP_FAIL("sp_lda_step: k = %lld must be in 1 .. %d", (long long)k, SP_LDA_MAX_K);
+    if (iters < 1) SP_FAIL("sp_lda_step: iters = %d must be at least 1", (int)iters);
+    if (!(alpha > 0.0) || std::isinf(alpha)) SP_FAIL("sp_lda_step: alpha = %g must be finite and > 0", alpha);
+    if (!(eta > 0.0) || std::isinf(eta)) SP_FAIL("sp_lda_step: eta = %g must be finite and > 0", eta);
+    if (!lda_shape_ok(V, D, k, iters, splits) || ldx < D || ldn < V || (d_delta && ldd < V) || (d_doc_topics && ldt < k))
+      SP_FAIL("sp_lda_step: bad shape V=%lld D=%lld k=%lld ldx=%lld ldn=%lld ldd=%lld ldt=%lld splits=%d", (long long)V,
+              (long long)D, (long long)k, (long long)ldx, (long long)ldn, (long long)ldd, (long long)ldt, (int)splits);
+    if (V > 0 && (!d_N || (D > 0 && !d_X))) SP_FAIL("sp_lda_step: X and N are required");
+    return lda_run<T>((const T*)d_X, ldx, V, D, (const T*)d_N, ldn, k, alpha, eta, iters, splits, (T*)d_delta, ldd,
+                      (T*)d_doc_topics, ldt, d_ws, ws_bytes, (hipStream_t)stream);
+  });
 }

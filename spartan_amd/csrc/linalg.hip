@@ -21,7 +21,7 @@
 // reads *d_info first and returns (negt_kernel writes zeros, so the GEMM calls, which cannot read the flag, add
 // nothing).  No kernel of a failed call takes the square root of a non-positive number or divides by one.
 // Square roots and divisions are the correctly rounded ones (Makefile: linalg.o).
-#include "sp_common.hpp"
+#include "sp_extras_common.hpp"
 #include "../../include/spartan_hip_extras.h"
 #include "../../include/spartan_hip_eig.h"
 
@@ -180,7 +180,6 @@ int trsm_launch(const T* L, int64_t ldl, int64_t n, T* B, int64_t ldb, int64_t m
   return 0;
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int64_t up4(int64_t v) { return (v + 3) & ~(int64_t)3; }
 
 // scratch a GEMM of the update may be handed: what its split-K wants -- unless the shape is one the bf16 split tier
@@ -231,8 +230,8 @@ int update(int32_t dtype, T* A, int64_t lda, int64_t n, int64_t r0, int64_t c0, 
 template <typename T>
 int potrf_run(int32_t dtype, T* A, int64_t lda, int64_t n, void* d_ws, int32_t* info, hipStream_t st) {
   const Scratch s = scratch_of(dtype, n);
-  T* negt = (T*)up256((size_t)(uintptr_t)d_ws);
-  void* gemm_ws = (void*)up256((size_t)(uintptr_t)negt + s.negt_bytes);
+  T* negt = (T*)sp_align256((size_t)(uintptr_t)d_ws);
+  void* gemm_ws = (void*)sp_align256((size_t)(uintptr_t)negt + s.negt_bytes);
   for (int64_t j0 = 0; j0 < n; j0 += OB) {
     const int64_t w = (n - j0) < OB ? (n - j0) : OB;
     if (j0 > 0 && update<T>(dtype, A, lda, n, j0, 0, w, negt, gemm_ws, info, st)) return 1;
@@ -257,37 +256,36 @@ int potrf_run(int32_t dtype, T* A, int64_t lda, int64_t n, void* d_ws, int32_t* 
 extern "C" size_t sp_potrf_workspace_bytes(int32_t dtype, int64_t n) {
   if (n < 1 || (dtype != SP_F32 && dtype != SP_F64)) return 256;
   const Scratch s = scratch_of(dtype, n);
-  return 256 + up256(s.negt_bytes) + 256 + s.gemm_bytes;
+  return 256 + sp_align256(s.negt_bytes) + 256 + s.gemm_bytes;
 }
 
 extern "C" int sp_potrf(int32_t dtype, void* d_A, int64_t lda, int64_t n, void* d_ws, size_t ws_bytes, int32_t* d_info,
                         void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64)
-    SP_FAIL("sp_potrf: dtype must be f32 or f64; convert with astype first");
-  if (n < 0) SP_FAIL("sp_potrf: bad size");
-  if (!d_info) SP_FAIL("sp_potrf: NULL info");
-  hipStream_t st = (hipStream_t)stream;
-  SP_HIP(hipMemsetAsync(d_info, 0, sizeof(int32_t), st));
-  if (n == 0) return 0;
-  if (n > 2147483647LL) SP_FAIL("sp_potrf: order too large");
-  if (!d_A) SP_FAIL("sp_potrf: NULL pointer");
-  if (lda < n) SP_FAIL("sp_potrf: leading dimension too small");
-  if (n > NB && (!d_ws || ws_bytes < sp_potrf_workspace_bytes(dtype, n))) SP_FAIL("sp_potrf: workspace too small");
-  if (dtype == SP_F32) return potrf_run<float>(dtype, (float*)d_A, lda, n, d_ws, d_info, st);
-  return potrf_run<double>(dtype, (double*)d_A, lda, n, d_ws, d_info, st);
+  return sp_float_dispatch("sp_potrf", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (n < 0) SP_FAIL("sp_potrf: bad size");
+    if (!d_info) SP_FAIL("sp_potrf: NULL info");
+    hipStream_t st = (hipStream_t)stream;
+    SP_HIP(hipMemsetAsync(d_info, 0, sizeof(int32_t), st));
+    if (n == 0) return 0;
+    if (n > 2147483647LL) SP_FAIL("sp_potrf: order too large");
+    if (!d_A) SP_FAIL("sp_potrf: NULL pointer");
+    if (lda < n) SP_FAIL("sp_potrf: leading dimension too small");
+    if (n > NB && (!d_ws || ws_bytes < sp_potrf_workspace_bytes(dtype, n))) SP_FAIL("sp_potrf: workspace too small");
+    return potrf_run<T>(dtype, (T*)d_A, lda, n, d_ws, d_info, st);
+  });
 }
 
 extern "C" int sp_trsm_rlt(int32_t dtype, const void* d_L, int64_t ldl, int64_t n, void* d_B, int64_t ldb, int64_t m,
                            void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64)
-    SP_FAIL("sp_trsm_rlt: dtype must be f32 or f64; convert with astype first");
-  if (n < 0 || m < 0) SP_FAIL("sp_trsm_rlt: bad sizes");
-  if (n == 0 || m == 0) return 0;
-  if (!d_L || !d_B) SP_FAIL("sp_trsm_rlt: NULL pointer");
-  if (ldl < n || ldb < n) SP_FAIL("sp_trsm_rlt: leading dimension too small");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SP_F32) return trsm_launch<float>((const float*)d_L, ldl, n, (float*)d_B, ldb, m, nullptr, st);
-  return trsm_launch<double>((const double*)d_L, ldl, n, (double*)d_B, ldb, m, nullptr, st);
+  return sp_float_dispatch("sp_trsm_rlt", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (n < 0 || m < 0) SP_FAIL("sp_trsm_rlt: bad sizes");
+    if (n == 0 || m == 0) return 0;
+    if (!d_L || !d_B) SP_FAIL("sp_trsm_rlt: NULL pointer");
+    if (ldl < n || ldb < n) SP_FAIL("sp_trsm_rlt: leading dimension too small");
+    return trsm_launch<T>((const T*)d_L, ldl, n, (T*)d_B, ldb, m, nullptr, (hipStream_t)stream);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -608,7 +606,7 @@ __global__ __launch_bounds__(256) void syevj_sort_kernel(const T* __restrict__ A
   }
 }
 
-size_t syevj_buffer_bytes(int32_t dtype, int64_t n) { return up256((size_t)n * (size_t)n * sp_dtype_size(dtype)); }
+size_t syevj_buffer_bytes(int32_t dtype, int64_t n) { return sp_align256((size_t)n * (size_t)n * sp_dtype_size(dtype)); }
 
 template <typename T>
 int syevj_read_word(const SyevjWord* d_word, SyevjWord* h, hipStream_t st) {
@@ -620,7 +618,7 @@ int syevj_read_word(const SyevjWord* d_word, SyevjWord* h, hipStream_t st) {
 template <typename T>
 int syevj_run(int32_t dtype, const T* A, int64_t lda, int n, T* W, T* V, int64_t ldv, void* d_ws, int32_t* info,
               int32_t* sweeps_out, hipStream_t st) {
-  char* base = (char*)up256((size_t)(uintptr_t)d_ws);
+  char* base = (char*)sp_align256((size_t)(uintptr_t)d_ws);
   SyevjWord* word = (SyevjWord*)base;
   const size_t nn = syevj_buffer_bytes(dtype, n);
   T* bufA[2] = {(T*)(base + 256), (T*)(base + 256 + 2 * nn)};
@@ -671,19 +669,18 @@ extern "C" size_t sp_syevj_workspace_bytes(int32_t dtype, int64_t n) {
 
 extern "C" int sp_syevj(int32_t dtype, void* d_A, int64_t lda, int64_t n, void* d_W, void* d_V, int64_t ldv, void* d_ws,
                         size_t ws_bytes, int32_t* d_info, int32_t* sweeps_out, void* stream) {
-  if (dtype != SP_F32 && dtype != SP_F64)
-    SP_FAIL("sp_syevj: dtype must be f32 or f64; convert with astype first");
-  if (n < 0) SP_FAIL("sp_syevj: bad size");
-  if (!d_info) SP_FAIL("sp_syevj: NULL info");
-  hipStream_t st = (hipStream_t)stream;
-  SP_HIP(hipMemsetAsync(d_info, 0, sizeof(int32_t), st));
-  if (sweeps_out) *sweeps_out = 0;
-  if (n == 0) return 0;
-  if (n > SYEVJ_MAX_ORDER) SP_FAIL("sp_syevj: order too large for the Jacobi solver");
-  if (!d_A || !d_W || !d_V) SP_FAIL("sp_syevj: NULL pointer");
-  if (lda < n || ldv < n) SP_FAIL("sp_syevj: leading dimension too small");
-  if (!d_ws || ws_bytes < sp_syevj_workspace_bytes(dtype, n)) SP_FAIL("sp_syevj: workspace too small");
-  if (dtype == SP_F32)
-    return syevj_run<float>(dtype, (const float*)d_A, lda, (int)n, (float*)d_W, (float*)d_V, ldv, d_ws, d_info, sweeps_out, st);
-  return syevj_run<double>(dtype, (const double*)d_A, lda, (int)n, (double*)d_W, (double*)d_V, ldv, d_ws, d_info, sweeps_out, st);
+  return sp_float_dispatch("sp_syevj", dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (n < 0) SP_FAIL("sp_syevj: bad size");
+    if (!d_info) SP_FAIL("sp_syevj: NULL info");
+    hipStream_t st = (hipStream_t)stream;
+    SP_HIP(hipMemsetAsync(d_info, 0, sizeof(int32_t), st));
+    if (sweeps_out) *sweeps_out = 0;
+    if (n == 0) return 0;
+    if (n > SYEVJ_MAX_ORDER) SP_FAIL("sp_syevj: order too large for the Jacobi solver");
+    if (!d_A || !d_W || !d_V) SP_FAIL("sp_syevj: NULL pointer");
+    if (lda < n || ldv < n) SP_FAIL("sp_syevj: leading dimension too small");
+    if (!d_ws || ws_bytes < sp_syevj_workspace_bytes(dtype, n)) SP_FAIL("sp_syevj: workspace too small");
+    return syevj_run<T>(dtype, (const T*)d_A, lda, (int)n, (T*)d_W, (T*)d_V, ldv, d_ws, d_info, sweeps_out, st);
+  });
 }

@@ -41,6 +41,24 @@ def _elsize(t):
   return t.element_size() if hasattr(t, 'element_size') else t.itemsize
 
 
+def _p(t):
+  """Where `t` lives in HBM as a pointer argument; NULL for None."""
+  return C.c_void_p(None if t is None else t.data_ptr())
+
+
+def _float_dtype(what, first, *others):
+  """The dtype of `first` for a launcher `what` that exists in float32 and float64 only: TypeError for an operand of
+  another dtype, or for one of `others` (None is skipped) whose dtype is not that of `first`, in the operands' order."""
+  dt = np_dtype_of(first)
+  for t in (first,) + others:
+    if t is None:
+      continue
+    _hip.refuse_not_float(np_dtype_of(t), what)
+    if np_dtype_of(t) != dt:
+      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, dt, np_dtype_of(t)))
+  return dt
+
+
 class Workspace(object):
   """Grow-only scratch blob for reduction partials (one per device)."""
 
@@ -151,22 +169,27 @@ def gemm_f32(a, b, c, accumulate=False):
   return c
 
 
-def rowdot_colsum(x, w, y, out, accumulate=False):
-  """out[c] (+)= sum_i x[i, c] * (x[i, :] . w - y[i]) in one pass over the fp32 row tile x [n, d] (y may be None);
-  False when the operands do not meet sp_rowdot_colsum_f32's layout (the caller then takes the two-launch form)."""
+def _rowdot_operands(x, w, y, out):
+  """(n, d, ldx, ldy, workspace) of the one-pass rowdot kernels, or None when the operands do not meet their layout."""
   _require_device(x, w, out)
   n, d = x.shape
-  lib = _hip.lib()
-  need = lib.sp_rowdot_colsum_workspace_bytes(n, d) if n else 256
+  need = _hip.lib().sp_rowdot_colsum_workspace_bytes(n, d) if n else 256
   ldx = x.stride(0) if n > 1 else d
   if (not need or x.stride(1) != 1 or ldx % 4 or (x.data_ptr() | w.data_ptr() | out.data_ptr()) % 16
       or any(np_dtype_of(t) != np.float32 for t in (x, w, out) + ((y,) if y is not None else ()))):
+    return None
+  return n, d, ldx, (y.stride(0) if y is not None and n > 1 else 1), _ws.get(need, x.device)
+
+
+def rowdot_colsum(x, w, y, out, accumulate=False):
+  """out[c] (+)= sum_i x[i, c] * (x[i, :] . w - y[i]) in one pass over the fp32 row tile x [n, d] (y may be None);
+  False when the operands do not meet sp_rowdot_colsum_f32's layout (the caller then takes the two-launch form)."""
+  ops = _rowdot_operands(x, w, y, out)
+  if ops is None:
     return False
-  ws = _ws.get(need, x.device)
-  check(lib.sp_rowdot_colsum_f32(C.c_void_p(x.data_ptr()), ldx, n, d, C.c_void_p(w.data_ptr()),
-                                 C.c_void_p(y.data_ptr() if y is not None else 0),
-                                 (y.stride(0) if y is not None and n > 1 else 1), C.c_void_p(out.data_ptr()),
-                                 1 if accumulate else 0, C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
+  n, d, ldx, ldy, ws = ops
+  check(_hip.lib().sp_rowdot_colsum_f32(_p(x), ldx, n, d, _p(w), _p(y), ldy, _p(out), 1 if accumulate else 0, _p(ws),
+                                        ws.numel(), _stream()))
   return True
 
 
@@ -174,20 +197,12 @@ def rowdot_link_colsum(x, w, y, out, link, accumulate=False):
   """out[c] (+)= sum_i x[i, c] * (link(x[i, :] . w) - y[i]) in one pass over the fp32 row tile x [n, d] (y may be None),
   link one of _hip.SP_LINK_*: sp_rowdot_link_colsum_f32.  False when the operands do not meet the kernel's layout
   (the caller then takes the launches the expression states); a link the library does not know is an error."""
-  _require_device(x, w, out)
-  n, d = x.shape
-  lib = _hip.lib()
-  need = lib.sp_rowdot_colsum_workspace_bytes(n, d) if n else 256
-  ldx = x.stride(0) if n > 1 else d
-  if (not need or x.stride(1) != 1 or ldx % 4 or (x.data_ptr() | w.data_ptr() | out.data_ptr()) % 16
-      or any(np_dtype_of(t) != np.float32 for t in (x, w, out) + ((y,) if y is not None else ()))):
+  ops = _rowdot_operands(x, w, y, out)
+  if ops is None:
     return False
-  ws = _ws.get(need, x.device)
-  check(lib.sp_rowdot_link_colsum_f32(C.c_void_p(x.data_ptr()), ldx, n, d, C.c_void_p(w.data_ptr()),
-                                      C.c_void_p(y.data_ptr() if y is not None else 0),
-                                      (y.stride(0) if y is not None and n > 1 else 1), int(link),
-                                      C.c_void_p(out.data_ptr()), 1 if accumulate else 0, C.c_void_p(ws.data_ptr()),
-                                      ws.numel(), _stream()))
+  n, d, ldx, ldy, ws = ops
+  check(_hip.lib().sp_rowdot_link_colsum_f32(_p(x), ldx, n, d, _p(w), _p(y), ldy, int(link), _p(out),
+                                             1 if accumulate else 0, _p(ws), ws.numel(), _stream()))
   return True
 
 
@@ -314,16 +329,14 @@ def potrf(a, info):
   its Cholesky factor L, the strict upper triangle zero (sp_potrf); `info`, a device int32, receives 0 or the order
   of the first leading minor that is not positive definite.  Nothing waits for the device."""
   _require_device(a, info)
-  dt = np_dtype_of(a)
-  _hip.refuse_not_float(dt, 'potrf')
+  dt = _float_dtype('potrf', a)
   assert a.dim() == 2 and a.shape[0] == a.shape[1] and np_dtype_of(info) == np.int32
   n = int(a.shape[0])
   assert n <= 1 or a.stride(1) == 1
   lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
   code = _hip.sp_dtype(dt)
   ws = _ws.get(lib.sp_potrf_workspace_bytes(code, n), a.device)
-  check(lib.sp_potrf(code, C.c_void_p(a.data_ptr()), _ld(a), n, C.c_void_p(ws.data_ptr()), ws.numel(),
-                     C.c_void_p(info.data_ptr()), _stream()))
+  check(lib.sp_potrf(code, _p(a), _ld(a), n, _p(ws), ws.numel(), _p(info), _stream()))
   return a
 
 
@@ -331,16 +344,14 @@ def trsm_rlt(b, l):
   """In place: b <- x with x . l^T = b, `l` square lower triangular (its upper triangle is not read), `b` [m, n]; both
   fp32 or both fp64, views with inner stride 1 (sp_trsm_rlt)."""
   _require_device(b, l)
-  dt = np_dtype_of(b)
-  _hip.refuse_not_float(dt, 'trsm_rlt')
-  _hip.refuse_not_float(np_dtype_of(l), 'trsm_rlt')
+  dt = _float_dtype('trsm_rlt', b)
+  _float_dtype('trsm_rlt', l)
   assert dt == np_dtype_of(l) and b.dim() == 2 and l.dim() == 2
   m, n = (int(v) for v in b.shape)
   assert tuple(l.shape) == (n, n), (b.shape, l.shape)
   assert n <= 1 or (b.stride(1) == 1 and l.stride(1) == 1)
   if m and n:
-    check(_hip.extras().sp_trsm_rlt(_hip.sp_dtype(dt), C.c_void_p(l.data_ptr()), _ld(l), n, C.c_void_p(b.data_ptr()),
-                                    _ld(b), m, _stream()))
+    check(_hip.extras().sp_trsm_rlt(_hip.sp_dtype(dt), _p(l), _ld(l), n, _p(b), _ld(b), m, _stream()))
   return b
 
 
@@ -351,8 +362,7 @@ def syevj(a, w, v, info):
   converge.  Returns the number of sweeps.  The call waits for the device once per sweep (a word that says whether
   the off-diagonal norm is below n u ||a||_F) and for nothing else."""
   _require_device(a, w, v, info)
-  dt = np_dtype_of(a)
-  _hip.refuse_not_float(dt, 'syevj')
+  dt = _float_dtype('syevj', a)
   assert a.dim() == 2 and a.shape[0] == a.shape[1] and np_dtype_of(info) == np.int32
   n = int(a.shape[0])
   assert np_dtype_of(w) == dt and np_dtype_of(v) == dt and tuple(w.shape) == (n,) and tuple(v.shape) == (n, n)
@@ -361,8 +371,8 @@ def syevj(a, w, v, info):
   code = _hip.sp_dtype(dt)
   ws = _ws.get(lib.sp_syevj_workspace_bytes(code, n), a.device)
   sweeps = C.c_int32(0)
-  check(lib.sp_syevj(code, C.c_void_p(a.data_ptr()), _ld(a), n, C.c_void_p(w.data_ptr()), C.c_void_p(v.data_ptr()), _ld(v),
-                     C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(info.data_ptr()), C.byref(sweeps), _stream()))
+  check(lib.sp_syevj(code, _p(a), _ld(a), n, _p(w), _p(v), _ld(v), _p(ws), ws.numel(), _p(info), C.byref(sweeps),
+                     _stream()))
   return int(sweeps.value)
 
 
@@ -372,9 +382,8 @@ def knn(q, x, k, dist2, idx, index_offset=0, splits=0):
   (sp_knn).  q, x: both fp32 or both fp64, views with inner stride 1; dist2 (their dtype) and idx (int64): contiguous
   [nq, k].  splits: 0 = the library chooses into how many ranges the points are cut, s >= 1 = min(s, np) ranges."""
   _require_device(q, x, dist2, idx)
-  dt = np_dtype_of(q)
-  _hip.refuse_not_float(dt, 'knn')
-  _hip.refuse_not_float(np_dtype_of(x), 'knn')
+  dt = _float_dtype('knn', q)
+  _float_dtype('knn', x)
   assert dt == np_dtype_of(x) == np_dtype_of(dist2) and np_dtype_of(idx) == np.int64
   assert q.dim() == 2 and x.dim() == 2 and q.shape[1] == x.shape[1], (q.shape, x.shape)
   nq, d = (int(v) for v in q.shape)
@@ -385,9 +394,8 @@ def knn(q, x, k, dist2, idx, index_offset=0, splits=0):
   code = _hip.sp_dtype(dt)
   need = lib.sp_knn_workspace_bytes(code, nq, n, d, k, int(splits))
   ws = _ws.get(need, q.device) if need else None
-  check(lib.sp_knn(code, C.c_void_p(q.data_ptr()), _ld(q), nq, C.c_void_p(x.data_ptr()), _ld(x), n, d, k,
-                   int(index_offset), int(splits), C.c_void_p(dist2.data_ptr()), C.c_void_p(idx.data_ptr()),
-                   C.c_void_p(ws.data_ptr() if need else 0), ws.numel() if need else 0, _stream()))
+  check(lib.sp_knn(code, _p(q), _ld(q), nq, _p(x), _ld(x), n, d, k, int(index_offset), int(splits), _p(dist2), _p(idx),
+                   _p(ws), ws.numel() if need else 0, _stream()))
   return dist2, idx
 
 
@@ -396,17 +404,15 @@ def knn_merge(cand_dist2, cand_idx, k, dist2, idx):
   index are padding (sp_knn_merge).  cand_dist2 (fp32 / fp64) and cand_idx (int64): [nq, m] views with inner stride 1
   and ONE row stride; dist2, idx: contiguous [nq, k]."""
   _require_device(cand_dist2, cand_idx, dist2, idx)
-  dt = np_dtype_of(cand_dist2)
-  _hip.refuse_not_float(dt, 'knn_merge')
+  dt = _float_dtype('knn_merge', cand_dist2)
   assert np_dtype_of(cand_idx) == np.int64 and np_dtype_of(idx) == np.int64 and np_dtype_of(dist2) == dt
   assert cand_dist2.dim() == 2 and tuple(cand_dist2.shape) == tuple(cand_idx.shape)
   nq, m = (int(v) for v in cand_dist2.shape)
   k = int(k)
   assert _ld(cand_dist2) == _ld(cand_idx), (cand_dist2.stride(), cand_idx.stride())
   assert tuple(dist2.shape) == (nq, k) and tuple(idx.shape) == (nq, k) and dist2.is_contiguous() and idx.is_contiguous()
-  check(_hip.extras().sp_knn_merge(_hip.sp_dtype(dt), C.c_void_p(cand_dist2.data_ptr()), C.c_void_p(cand_idx.data_ptr()),
-                                   _ld(cand_dist2), nq, m, k, C.c_void_p(dist2.data_ptr()), C.c_void_p(idx.data_ptr()),
-                                   _stream()))
+  check(_hip.extras().sp_knn_merge(_hip.sp_dtype(dt), _p(cand_dist2), _p(cand_idx), _ld(cand_dist2), nq, m, k, _p(dist2),
+                                   _p(idx), _stream()))
   return dist2, idx
 
 
@@ -416,13 +422,11 @@ def apsp(d, info):
   blocked Floyd-Warshall, a candidate d[i][k] + d[k][j] wins only if it is smaller).  `info`, a device int32, receives
   0, or 1 if an off-diagonal entry is NaN or negative (`d` is then unspecified).  Nothing waits for the device."""
   _require_device(d, info)
-  dt = np_dtype_of(d)
-  _hip.refuse_not_float(dt, 'apsp')
+  dt = _float_dtype('apsp', d)
   assert d.dim() == 2 and d.shape[0] == d.shape[1] and np_dtype_of(info) == np.int32
   n = int(d.shape[0])
   assert n <= 1 or d.stride(1) == 1
-  check(_hip.extras().sp_apsp(_hip.sp_dtype(dt), C.c_void_p(d.data_ptr()), _ld(d), n, C.c_void_p(info.data_ptr()),
-                              _stream()))
+  check(_hip.extras().sp_apsp(_hip.sp_dtype(dt), _p(d), _ld(d), n, _p(info), _stream()))
   return d
 
 
@@ -432,16 +436,14 @@ def graph_from_knn(dist, idx, w):
   smallest weight stated for it in either direction, on both sides; idx < 0 is padding (sp_graph_from_knn).  `w`: of
   dist's dtype, a view with inner stride 1."""
   _require_device(dist, idx, w)
-  dt = np_dtype_of(dist)
-  _hip.refuse_not_float(dt, 'graph_from_knn')
+  dt = _float_dtype('graph_from_knn', dist)
   assert np_dtype_of(idx) == np.int64 and np_dtype_of(w) == dt
   assert dist.dim() == 2 and tuple(dist.shape) == tuple(idx.shape)
   n, k = (int(v) for v in dist.shape)
   assert tuple(w.shape) == (n, n) and (n <= 1 or w.stride(1) == 1)
   assert k <= 1 or (dist.stride(1) == 1 and idx.stride(1) == 1)
   assert n <= 1 or _ld(dist) == _ld(idx), (dist.stride(), idx.stride())
-  check(_hip.extras().sp_graph_from_knn(_hip.sp_dtype(dt), C.c_void_p(dist.data_ptr()), C.c_void_p(idx.data_ptr()),
-                                        _ld(dist), n, k, C.c_void_p(w.data_ptr()), _ld(w), _stream()))
+  check(_hip.extras().sp_graph_from_knn(_hip.sp_dtype(dt), _p(dist), _p(idx), _ld(dist), n, k, _p(w), _ld(w), _stream()))
   return w
 
 
@@ -452,11 +454,7 @@ def als_solve(r, y, la, alpha, implicit, x, info):
   receives 1 + the lowest row whose system is not positive definite if it is still 0; that row of x is NaN.  TypeError
   for other dtypes, ValueError for shapes that do not fit or f outside 1 .. 64.  Nothing waits for the device."""
   _require_device(r, y, x, info)
-  dt = np_dtype_of(r)
-  _hip.refuse_not_float(dt, 'als_solve')
-  _hip.refuse_not_float(np_dtype_of(y), 'als_solve')
-  if dt != np_dtype_of(y):
-    raise TypeError('als_solve: operands of two dtypes (%s, %s); convert with astype first' % (dt, np_dtype_of(y)))
+  dt = _float_dtype('als_solve', r, y)
   if r.dim() != 2 or y.dim() != 2 or r.shape[1] != y.shape[0]:
     raise ValueError('als_solve: shapes %s and %s do not fit' % (tuple(r.shape), tuple(y.shape)))
   m, n = (int(v) for v in r.shape)
@@ -472,9 +470,8 @@ def als_solve(r, y, la, alpha, implicit, x, info):
   lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
   code = _hip.sp_dtype(dt)
   ws = _ws.get(lib.sp_als_solve_workspace_bytes(code, m, n, f, int(bool(implicit))), r.device)
-  check(lib.sp_als_solve(code, C.c_void_p(r.data_ptr()), _ld(r), m, n, C.c_void_p(y.data_ptr()), _ld(y), f, float(la),
-                         float(alpha), int(bool(implicit)), C.c_void_p(x.data_ptr()), _ld(x),
-                         C.c_void_p(info.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
+  check(lib.sp_als_solve(code, _p(r), _ld(r), m, n, _p(y), _ld(y), f, float(la), float(alpha), int(bool(implicit)), _p(x),
+                         _ld(x), _p(info), _p(ws), ws.numel(), _stream()))
   return x
 
 
@@ -487,11 +484,7 @@ def fuzzy_step(points, centers, m, labels, sums, wsum, u=None, splits=0):
   min(s, ceil(n / 64)) ranges.  TypeError for other or mixed dtypes, ValueError for m that is not finite and > 1,
   k < 1 or shapes that do not fit -- all before any launch.  Nothing waits for the device."""
   _require_device(points, centers, labels, sums, wsum, u)
-  dt = np_dtype_of(points)
-  for t in (points, centers, sums, wsum) + (() if u is None else (u,)):
-    _hip.refuse_not_float(np_dtype_of(t), 'fuzzy_step')
-    if np_dtype_of(t) != dt:
-      raise TypeError('fuzzy_step: operands of two dtypes (%s, %s); convert with astype first' % (dt, np_dtype_of(t)))
+  dt = _float_dtype('fuzzy_step', points, centers, sums, wsum, u)
   m = float(m)
   if not (m > 1.0 and m != float('inf')):
     raise ValueError('fuzzy_step: m = %r must be finite and > 1' % (m,))
@@ -512,12 +505,8 @@ def fuzzy_step(points, centers, m, labels, sums, wsum, u=None, splits=0):
   lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
   code = _hip.sp_dtype(dt)
   ws = _ws.get(lib.sp_fuzzy_step_workspace_bytes(code, n, k, d, int(splits)), points.device)
-  check(lib.sp_fuzzy_step(code, C.c_void_p(points.data_ptr()), _ld(points), n, C.c_void_p(centers.data_ptr()),
-                          _ld(centers), k, d, m, int(splits),
-                          None if labels is None else C.c_void_p(labels.data_ptr()), C.c_void_p(sums.data_ptr()),
-                          _ld(sums), C.c_void_p(wsum.data_ptr()),
-                          None if u is None else C.c_void_p(u.data_ptr()), k if u is None else _ld(u),
-                          C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
+  check(lib.sp_fuzzy_step(code, _p(points), _ld(points), n, _p(centers), _ld(centers), k, d, m, int(splits), _p(labels),
+                          _p(sums), _ld(sums), _p(wsum), _p(u), k if u is None else _ld(u), _p(ws), ws.numel(), _stream()))
   return labels, sums, wsum, u
 
 
@@ -544,11 +533,7 @@ def lda_step(x, n, alpha, eta, iters, delta=None, doc_topics=None, splits=0):
   for other or mixed dtypes, ValueError for k outside 1 .. 128, iters < 1, alpha or eta not finite and > 0 or shapes
   that do not fit -- all before any launch.  Nothing waits for the device."""
   _require_device(x, n, delta, doc_topics)
-  dt = np_dtype_of(x)
-  for t in (x, n) + tuple(o for o in (delta, doc_topics) if o is not None):
-    _hip.refuse_not_float(np_dtype_of(t), 'lda_step')
-    if np_dtype_of(t) != dt:
-      raise TypeError('lda_step: operands of two dtypes (%s, %s); convert with astype first' % (dt, np_dtype_of(t)))
+  dt = _float_dtype('lda_step', x, n, delta, doc_topics)
   if x.dim() != 2 or n.dim() != 2 or x.shape[0] != n.shape[1]:
     raise ValueError('lda_step: shapes %s and %s do not fit' % (tuple(x.shape), tuple(n.shape)))
   v, d = (int(s) for s in x.shape)
@@ -563,11 +548,9 @@ def lda_step(x, n, alpha, eta, iters, delta=None, doc_topics=None, splits=0):
   lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
   code = _hip.sp_dtype(dt)
   ws = _ws.get(lib.sp_lda_step_workspace_bytes(code, v, d, k, iters, int(splits)), x.device)
-  check(lib.sp_lda_step(code, C.c_void_p(x.data_ptr()), _ld(x), v, d, C.c_void_p(n.data_ptr()), _ld(n), k, alpha, eta,
-                        iters, int(splits),
-                        None if delta is None else C.c_void_p(delta.data_ptr()), v if delta is None else _ld(delta),
-                        None if doc_topics is None else C.c_void_p(doc_topics.data_ptr()),
-                        k if doc_topics is None else _ld(doc_topics), C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
+  check(lib.sp_lda_step(code, _p(x), _ld(x), v, d, _p(n), _ld(n), k, alpha, eta, iters, int(splits), _p(delta),
+                        v if delta is None else _ld(delta), _p(doc_topics), k if doc_topics is None else _ld(doc_topics),
+                        _p(ws), ws.numel(), _stream()))
   return delta, doc_topics
 
 
