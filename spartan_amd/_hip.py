@@ -307,6 +307,12 @@ _EXTRAS_ABI = {
                                   _vp, _sz, _vp]),
         'sp_lda_step_workspace_bytes': (_sz, [_i32, _i64, _i64, _i64, _i32, _i32]),
     },
+    'spartan_hip_spectral.h': {
+        'sp_affinity_degree_workspace_bytes': (_sz, [_i32, _i64, _i64, _i64]),
+        'sp_affinity_degree': (C.c_int, [_i32, _i32, _f64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+        'sp_affinity_matrix': (C.c_int, [_i32, _i32, _f64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64,
+                                         _vp]),
+    },
 }
 EXPORTS_EXTRAS = list(_EXTRAS_ABI['spartan_hip_extras.h'])
 EXPORTS_EIG = list(_EXTRAS_ABI['spartan_hip_eig.h'])
@@ -315,14 +321,33 @@ EXPORTS_GRAPH = list(_EXTRAS_ABI['spartan_hip_graph.h'])
 EXPORTS_ALS = list(_EXTRAS_ABI['spartan_hip_als.h'])
 EXPORTS_FUZZY = list(_EXTRAS_ABI['spartan_hip_fuzzy.h'])
 EXPORTS_LDA = list(_EXTRAS_ABI['spartan_hip_lda.h'])
+EXPORTS_SPECTRAL = list(_EXTRAS_ABI['spartan_hip_spectral.h'])
 KNN_MAX_K = 128       # SP_KNN_MAX_K of spartan_hip_knn.h
 SP_ALS_MAX_F = 64     # of spartan_hip_als.h
 SP_LDA_MAX_K = 128    # of spartan_hip_lda.h
+SP_AFF_METRICS = {'rbf': 0, 'euclidean': 1, 'manhattan': 2}   # SP_AFF_* of spartan_hip_spectral.h
+
+
+def check_affinity_params(metric, gamma, what='affinity'):
+  """(the library's code of `metric`, gamma as a float), or what sp_affinity_* refuses: NotImplementedError for
+  'scaled_euclidean', ValueError for an unknown metric or a gamma that is not finite.  The one copy: the launchers, the
+  backend and the NumPy bodies of examples/_spectral.py all refuse through it."""
+  if metric == 'scaled_euclidean':
+    raise NotImplementedError("%s: 'scaled_euclidean' is refused: the reference calls np.square(X, Y), which writes X "
+                              "squared INTO its second operand, so its result depends on the order in which the pairs "
+                              "are visited" % what)
+  if metric not in SP_AFF_METRICS:
+    raise ValueError('%s: unknown metric %r (%s)' % (what, metric, ' '.join(sorted(SP_AFF_METRICS))))
+  gamma = float(gamma)
+  if gamma != gamma or gamma in (float('inf'), float('-inf')):
+    raise ValueError('%s: gamma = %r must be finite' % (what, gamma))
+  return SP_AFF_METRICS[metric], gamma
 _extras = None
 
 
 def extras():
-  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve, fuzzy_step, lda_step);
+  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve, fuzzy_step, lda_step,
+  affinity_degree / affinity_matrix);
   raises if it has not been built."""
   global _extras
   if _extras is None:

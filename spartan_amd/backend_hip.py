@@ -1405,6 +1405,43 @@ class HipBackend(object):
     kernels.lda_step(x, n, alpha, eta, iters, delta=delta, doc_topics=doc_topics, splits=splits)
     return delta, doc_topics
 
+  def affinity_degree(self, x, y, metric='rbf', gamma=1.0):
+    """The degrees D_i = sum_j a(x_i, y_j) of the rows of `x` [m, d] against ALL rows of `y` [n, d] as a NEW tensor [m]
+    (sp_affinity_degree: the affinities stay in registers, nothing of size m x n is allocated).  metric: 'rbf'
+    (a = exp(-gamma d2)), 'euclidean' (sqrt(d2)) or 'manhattan' (sum_f |x_f - y_f|), the distance in the difference
+    form.  Both operands fp32 or both fp64.  The bits of D_i depend on row i of x and on y alone, so a band of rows
+    computed alone gives the bits the whole gives.  The library issues one kernel, or two when n > 448 (the columns
+    are then cut into ranges whose partial degrees a second kernel adds); the call counts as one launch when m > 0
+    and as none otherwise, and never waits for the device.  Refusals: kernels.affinity_degree's."""
+    x, y = self._as_device(x), self._as_device(y)
+    dt, m, _, _ = kernels.affinity_operands('affinity_degree', x, y)
+    deg = self.empty((m,), dt)
+    if not m:
+      _hip.check_affinity_params(metric, gamma, 'affinity_degree')    # (with rows the launcher refuses)
+    else:
+      before = self.launches
+      kernels.affinity_degree(self._knn_rows(x), self._knn_rows(y), metric, gamma, deg)
+      self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
+    return deg
+
+  def affinity_matrix(self, x, r0, y, metric='rbf', gamma=1.0, scale=None):
+    """The affinities of the rows of `x` [m, d] -- points r0 .. r0 + m - 1 of `y` [n, d] -- against all rows of `y` as a
+    NEW tensor [m, n] (sp_affinity_matrix, one workgroup per 64 x 64 tile, written exactly once).  Without `scale` the
+    plain a_ij; with `scale` [n] the normalised matrix of spectral clustering, a_ij * (scale[r0 + i] * scale[j]) with
+    exactly 1 at j = r0 + i -- symmetric bit for bit when the bands are put together.  Metrics and dtypes as
+    affinity_degree.  One kernel; the call counts as one launch when m > 0 and n > 0 and as none otherwise, and never
+    waits for the device.  Refusals: kernels.affinity_matrix's (they come before the launch and before it is
+    counted)."""
+    x, y = self._as_device(x), self._as_device(y)
+    scale = None if scale is None else self._as_device(scale)
+    dt, m, n, _ = kernels.affinity_operands('affinity_matrix', x, y, scale)
+    before = self.launches
+    out = self.empty((m, n), dt)
+    kernels.affinity_matrix(self._knn_rows(x), r0, self._knn_rows(y), metric, gamma, out,
+                            scale=None if scale is None else self.contiguous(scale))
+    self.launches = before + (1 if m and n else 0)   # (a strided operand's copy belongs to the call)
+    return out
+
   def convolve(self, image, filters):
     """stencil.py:29-45 as a GEMM: P[(n, x, y), (c, i, j)] = image[n, c, x+i, y+j] (0 beyond the edge) by one strided
     box copy per (c, i, j); P . filters[(c, i, j), f] on the MFMA GEMM; back to [n, f, x, y]."""

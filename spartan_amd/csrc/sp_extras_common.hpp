@@ -1,7 +1,7 @@
-// What the kernels of libspartan_hip_extras.so share (linalg, knn, apsp, als, fuzzy, lda; the main library's sources do
-// not include this file).  Every piece carries a numerical contract -- the order of an accumulation, the order in which
-// partials are added -- that tests pin bit for bit: one copy, so that a fix reaches every caller.  Look here before
-// copying a piece out of a neighbouring kernel file.
+// What the kernels of libspartan_hip_extras.so share (linalg, knn, apsp, als, fuzzy, lda, spectral; the main library's
+// sources do not include this file).  Every piece carries a numerical contract -- the order of an accumulation, the
+// order in which partials are added -- that tests pin bit for bit: one copy, so that a fix reaches every caller.  Look
+// here before copying a piece out of a neighbouring kernel file.
 #pragma once
 #include "sp_common.hpp"
 
@@ -33,7 +33,7 @@ __device__ __forceinline__ double pow_t(double a, double b) { return pow(a, b); 
 // the parts of a workspace start 256 bytes apart at the least
 inline size_t sp_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// ---- the 64 x 64 squared-distance tile of sp_fuzzy_step and sp_knn ---------------------------------------------------
+// ---- the 64 x 64 squared-distance tile of sp_fuzzy_step, sp_knn and sp_affinity_* ------------------------------
 constexpr int SP_D2_DC = 16;        // features per chunk
 constexpr int SP_D2_PITCH = 68;     // elements between the feature rows of a staged chunk (64 + 4: 16-byte aligned rows)
 
@@ -44,8 +44,9 @@ constexpr int SP_D2_PITCH = 68;     // elements between the feature rows of a st
 // while this one is used.  Every d2 is ONE accumulator that starts at 0 and takes (x_j - c_j)^2 for j = 0, 1, ... in
 // turn.  Rows >= n of X, rows >= k of C and features >= d load 0.  Every thread of the workgroup calls it (it
 // synchronises the workgroup).  knn_scan_kernel has these lines written out in its own loop and says why: a change here
-// belongs there as well.
-template <typename T>
+// belongs there as well.  L1 (sp_affinity_*'s 'manhattan'): the term is |x_j - c_j| instead, everything else the same;
+// the default leaves the squared-distance instantiations as they were.
+template <typename T, bool L1 = false>
 __device__ __forceinline__ void sp_d2_tile(const T* __restrict__ X, int64_t ldx, int64_t n, int64_t r0,
                                            const T* __restrict__ C, int64_t ldc, int64_t k, int64_t c0, int64_t d, T* xs,
                                            T* cs, int tid, T (&acc)[4][4]) {
@@ -89,7 +90,7 @@ __device__ __forceinline__ void sp_d2_tile(const T* __restrict__ X, int64_t ldx,
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
             const T t = xv.v[a] - cv.v[b];
-            acc[a][b] = acc[a][b] + t * t;
+            acc[a][b] = acc[a][b] + (L1 ? abs_t(t) : t * t);
           }
       }
     } else {
@@ -101,7 +102,7 @@ __device__ __forceinline__ void sp_d2_tile(const T* __restrict__ X, int64_t ldx,
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
             const T t = xv.v[a] - cv.v[b];
-            acc[a][b] = acc[a][b] + t * t;
+            acc[a][b] = acc[a][b] + (L1 ? abs_t(t) : t * t);
           }
       }
     }

@@ -9,5 +9,7 @@ symmetric eigenproblem of the small B . B^T on sp_syevj) and `pca` (PCA on that 
 embeds with sp_syevj; `als` (alternating least squares) solves every row's normal equations of a half-step in sp_als_solve;
 `fuzzy_kmeans` runs one sp_fuzzy_step (memberships, labels and weighted sums fused) per row tile and iteration;
 `lda.learn_topics` (LDA by collapsed variational Bayes) runs one sp_lda_step (the per-document loops fused) per tile of
-documents and pass.
+documents and pass; `spectral_clustering.spectral_cluster` finds the degrees with one sp_affinity_degree and writes the
+normalised affinity matrix with one sp_affinity_matrix per row band of the points (the affinity matrix itself is never
+stored), and `lanczos.solve` (float64 on the host around `dot`) hands its leading Ritz vectors to KMeans.
 Like `sort` they are imported on first use, not with the package."""

@@ -554,6 +554,57 @@ def lda_step(x, n, alpha, eta, iters, delta=None, doc_topics=None, splits=0):
   return delta, doc_topics
 
 
+def affinity_operands(what, x, y, *others):
+  """(dtype, m, n, d) of the operands of an affinity launcher, or its TypeError / ValueError."""
+  dt = _float_dtype(what, x, y, *others)
+  if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+    raise ValueError('%s: shapes %s and %s do not fit' % (what, tuple(x.shape), tuple(y.shape)))
+  return dt, int(x.shape[0]), int(y.shape[0]), int(x.shape[1])
+
+
+def affinity_degree(x, y, metric, gamma, deg):
+  """deg[i] <- sum_j a(x_i, y_j) over all rows of `y` (sp_affinity_degree; include/spartan_hip_spectral.h states the
+  measures and the order of the sum): `x` [m, d] and `y` [n, d], both fp32 or both fp64, views with inner stride 1;
+  deg [m] contiguous, of their dtype.  metric: 'rbf' (exp(-gamma d2)), 'euclidean', 'manhattan'.  Nothing of size m x n
+  is stored.  TypeError for other or mixed dtypes, ValueError for an unknown metric, a gamma that is not finite or
+  shapes that do not fit, NotImplementedError for 'scaled_euclidean' -- all before any launch.  Nothing waits for the
+  device."""
+  _require_device(x, y, deg)
+  dt, m, n, d = affinity_operands('affinity_degree', x, y, deg)
+  code_m, gamma = _hip.check_affinity_params(metric, gamma, 'affinity_degree')
+  if tuple(deg.shape) != (m,):
+    raise ValueError('affinity_degree: a target of shape %s for %d rows' % (tuple(deg.shape), m))
+  assert deg.is_contiguous()
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  need = lib.sp_affinity_degree_workspace_bytes(code, m, n, d)
+  ws = _ws.get(need, x.device) if need else None
+  check(lib.sp_affinity_degree(code, code_m, gamma, _p(x), _ld(x), m, _p(y), _ld(y), n, d, _p(deg), _p(ws),
+                               ws.numel() if need else 0, _stream()))
+  return deg
+
+
+def affinity_matrix(x, r0, y, metric, gamma, out, scale=None):
+  """out[i, j] <- a(x_i, y_j), where row i of `x` [m, d] is point r0 + i of the n points `y` [n, d]; with `scale` [n]
+  (contiguous): a_ij * (scale[r0 + i] * scale[j]) and exactly 1 at j = r0 + i (sp_affinity_matrix;
+  include/spartan_hip_spectral.h).  Operands all fp32 or all fp64, views with inner stride 1; out [m, n] the same.
+  Refusals as affinity_degree's, and ValueError for r0 < 0 or r0 + m > n.  Nothing waits for the device."""
+  _require_device(x, y, out, scale)
+  dt, m, n, d = affinity_operands('affinity_matrix', x, y, out, scale)
+  code_m, gamma = _hip.check_affinity_params(metric, gamma, 'affinity_matrix')
+  r0 = int(r0)
+  if r0 < 0 or r0 + m > n:
+    raise ValueError('affinity_matrix: rows %d .. %d are not among the %d points' % (r0, r0 + m, n))
+  if scale is not None and tuple(scale.shape) != (n,):
+    raise ValueError('affinity_matrix: a scale of shape %s for %d points' % (tuple(scale.shape), n))
+  if tuple(out.shape) != (m, n):
+    raise ValueError('affinity_matrix: a target of shape %s for %d rows and %d points' % (tuple(out.shape), m, n))
+  assert (n <= 1 or out.stride(1) == 1) and (scale is None or scale.is_contiguous())
+  check(_hip.extras().sp_affinity_matrix(_hip.sp_dtype(dt), code_m, gamma, _p(x), _ld(x), m, r0, _p(y), _ld(y), n, d,
+                                         _p(scale), _p(out), _ld(out), _stream()))
+  return out
+
+
 def gather_rows(src, idx):
   """src[idx] along axis 0 for a contiguous tensor and a device int64 index vector (filter.py:50-75)."""
   _require_device(src, idx)
