@@ -324,6 +324,30 @@ size_t sp_gemm_split_workspace_bytes(int32_t dtype, int64_t M, int64_t N, int64_
 int sp_gemm_ws(int32_t dtype, const void* d_A, int64_t lda, const void* d_B, int64_t ldb, void* d_C,
                int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t accumulate, void* d_ws,
                size_t ws_bytes, void* stream);
+/* The split tier's cut as a step of its own, for an operand that is multiplied more than once.
+ * sp_gemm_image_bytes: the bytes of one fp32 operand's image buffer -- a 256-byte head whose first word is that
+ * operand's own window flag, then its three bf16 images [ceil(K / 16)][rows][16]; 0 for another dtype, or rows or K < 1.
+ * side 0 is A [rows][K]; side 1 is B [K][rows], `rows` being B's column count.
+ * sp_gemm_cut: clears the head and cuts d_X (leading dimension ld elements; 16-byte aligned, ld % 4 == 0: the tier's
+ * layout, anything else is an error) into d_img (256-byte aligned).  What it writes is what sp_gemm_ws writes into its
+ * workspace for that operand.
+ * sp_gemm_ws_images: sp_gemm_ws with either operand's images handed in.  d_imgA / d_imgB may each be NULL (that
+ * operand is cut into d_ws as sp_gemm_ws does, and d_ws needs room for those images only: 512 bytes plus
+ * sp_gemm_image_bytes(...) - 256 per operand cut there; none at all when both come cut).  *_img_rows: the rows the
+ * buffer was cut with; *_row0: the first of the M (N) rows of it that this product takes, so a row block of A or a
+ * column block of B of a prepared operand needs no second cut (d_A / d_B then point at the block itself).  The raw
+ * operands are always required: the gated fp32 kernel reads them when a window flag is set, and the choice of tier
+ * looks at the shape and at THEIR layout only -- never at whether images came --, so the result has the same bits
+ * with and without them.  Where the fp32 tier runs the images are ignored.  sp_gemm_ws is this with both NULL. */
+size_t sp_gemm_image_bytes(int32_t dtype, int32_t side, int64_t rows, int64_t K);
+/* How many cut kernels this process has launched so far, through any of the entry points (one per operand cut). */
+int64_t sp_gemm_cut_launches(void);
+int sp_gemm_cut(int32_t side, const void* d_X, int64_t ld, int64_t rows, int64_t K, void* d_img, size_t img_bytes,
+                void* stream);
+int sp_gemm_ws_images(int32_t dtype, const void* d_A, int64_t lda, const void* d_imgA, int64_t a_img_rows,
+                      int64_t a_row0, const void* d_B, int64_t ldb, const void* d_imgB, int64_t b_img_rows,
+                      int64_t b_row0, void* d_C, int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t accumulate,
+                      void* d_ws, size_t ws_bytes, void* stream);
 
 /* Matrix . vector products (dot.py:180-183, dot_map2_np_mapper with a 1-D rhs;
  * the lreg step X.w and X^T.r) are HBM-bound and have no GEMM entry point:

@@ -11,6 +11,7 @@ import collections
 import contextlib
 import os
 import time
+import weakref
 
 import ctypes
 
@@ -120,6 +121,104 @@ class _Fit(object):
       self.note(dst, origin=src)
     else:
       self.labels.pop(dst.data_ptr(), None)        # anything else written into a known label tile: forget it
+
+
+class _GemmImageCache(object):
+  """The split-tier images (kernels.gemm_prepare) of the operands HipBackend.dot has seen more than once.
+
+  INVARIANT: an entry's images are the cut of the bytes its view (storage, offset, shape, strides) holds now.  It is kept
+  by construction, not by comparing bytes: an entry records its storage's `version`, every path that writes into an
+  existing array moves that version on (devarray.note_write; DESIGN.md lists the paths), and an entry whose version is
+  not the storage's is dropped when it is looked at.  The storage is held weakly and takes its entries along when it
+  dies, so an address that is handed out again never meets an old entry.
+
+  POLICY: the first product that shows an operand only notes it (the product cuts into the pooled workspace, as a call
+  without the cache does); the second cuts it into a buffer that is kept; later ones reuse the buffer.  Kept buffers stay
+  under `budget` bytes, least recently used first out.  `prepare(x, side)` makes a handle with `.nbytes`.
+
+  The kept buffers are device memory beside the tile store's pool: clear() gives them back, devarray.trim_pool() calls
+  it, and so does a `prepare` that finds no room.  At most MAX_ENTRIES views are remembered, sightings included (the
+  oldest goes first).  One thread: a storage's death may run drop_storage() in the middle of operand(), which only ever
+  removes entries of a storage that operand() is not looking at -- it holds a reference to its own."""
+  MAX_ENTRIES = 256
+
+  def __init__(self, prepare, budget=2 << 30, enabled=True):
+    self.prepare, self.budget, self.enabled = prepare, int(budget), bool(enabled)
+    self._entries = collections.OrderedDict()     # key -> [version, handle or None]; least recently used first
+    self._storages = {}                           # id(storage) -> (weak reference, set of keys)
+    self.stats = {'cuts': 0, 'reuses': 0, 'kept_bytes': 0, 'evictions': 0}
+
+  def _drop(self, key):
+    entry = self._entries.pop(key, None)
+    if entry is None:
+      return
+    if entry[1] is not None:
+      self.stats['kept_bytes'] -= entry[1].nbytes
+    ref_keys = self._storages.get(key[0])
+    if ref_keys is not None:
+      ref_keys[1].discard(key)
+      if not ref_keys[1]:
+        del self._storages[key[0]]
+
+  def drop_storage(self, storage_id):
+    """Forget what is known of a storage: it has been written into, or it has died."""
+    ref_keys = self._storages.get(storage_id)
+    for key in list(ref_keys[1]) if ref_keys is not None else ():
+      self._drop(key)
+
+  def wrote(self, t):
+    storage = getattr(t, 'storage', None)
+    if storage is not None:
+      self.drop_storage(id(storage))
+
+  def clear(self):
+    for key in list(self._entries):
+      self._drop(key)
+
+  def operand(self, x, side):
+    """The images to hand the product for operand `x` (side 0: left, 1: right), or None: let the product cut it."""
+    storage = getattr(x, 'storage', None)
+    if not self.enabled or type(x) is not D.DevArray or getattr(storage, 'version', -1) < 0:
+      if storage is not None:
+        self.drop_storage(id(storage))      # (exported since it was kept: its buffers go)
+      self.stats['cuts'] += 1
+      return None
+    key = (id(storage), x.offset, x.shape, x.strides, side)
+    entry = self._entries.get(key)
+    if entry is not None and entry[0] != storage.version:     # written since: as if never seen
+      self._drop(key)
+      entry = None
+    if entry is None:
+      ref_keys = self._storages.get(key[0])
+      if ref_keys is None:
+        sid = key[0]
+        ref_keys = self._storages[sid] = (weakref.ref(storage, lambda _, sid=sid: self.drop_storage(sid)), set())
+      ref_keys[1].add(key)
+      self._entries[key] = [storage.version, None]
+      while len(self._entries) > self.MAX_ENTRIES:
+        self._drop(next(iter(self._entries)))
+      self.stats['cuts'] += 1
+      return None
+    self._entries.move_to_end(key)
+    if entry[1] is not None:
+      self.stats['reuses'] += 1
+      return entry[1]
+    try:
+      handle = self.prepare(x, side)
+    except _hip.HipError:          # no room for a kept buffer: give back what is kept, the product cuts for itself
+      self.clear()
+      self.stats['cuts'] += 1
+      return None
+    self.stats['cuts'] += 1
+    if handle.nbytes <= self.budget:
+      entry[1] = handle
+      self.stats['kept_bytes'] += handle.nbytes
+      for old in [k for k, e in self._entries.items() if e[1] is not None and k != key]:
+        if self.stats['kept_bytes'] <= self.budget:
+          break
+        self._drop(old)
+        self.stats['evictions'] += 1
+    return handle
 
 
 class _HostCopyLater(object):
@@ -328,9 +427,19 @@ class HipBackend(object):
       rng_seed = (int(time.time() * 100000) + os.getpid()) & (2**63 - 1)
     self._rng_seed, self._rng_offset = rng_seed, 0
     self._lowered = self._lowered_type()
+    # the split-tier images of dot()'s operands (SP_GEMM_IMAGE_CACHE=0, read here, keeps none)
+    self._gemm_images = _GemmImageCache(kernels.gemm_prepare, enabled=os.environ.get('SP_GEMM_IMAGE_CACHE', '1') != '0')
+    D.on_trim(self._gemm_images.clear)
 
   _lowered_type = _Lowered      # (jit_seed's backend has a table that keeps nothing)
   lowering_hits = property(lambda self: self._lowered.hits)
+  # cuts: operands cut (by a product into the workspace, or into a buffer); reuses: operands that came from a kept buffer
+  gemm_image_stats = property(lambda self: dict(self._gemm_images.stats))
+
+  def _wrote(self, t):
+    """`t`, an array that existed before this call, is written by it: what was derived from its bytes is void."""
+    D.note_write(t)
+    self._gemm_images.wrote(t)
 
   # -- memory -------------------------------------------------------------------
   def empty(self, shape, dtype):
@@ -444,6 +553,7 @@ class HipBackend(object):
       src = src.reshape(view.shape)
     if view.numel() == 0:
       return
+    self._wrote(dst)
     if self.dtype_of(view) != self.dtype_of(src):
       raise _hip.HipError('paste: dtype mismatch %s vs %s' % (self.dtype_of(view), self.dtype_of(src)))
     nd = view.dim()
@@ -466,6 +576,7 @@ class HipBackend(object):
     src = self.contiguous(src)
     if not dst.is_contiguous():
       raise _hip.HipError('update target must be a dense tile')
+    self._wrote(dst)
     kernels.update(dst, ul, lr, src, self.reducer_name(reducer), mask_mode, mask)
     if self._fit is not None:
       self._fit.wrote(dst, ul, lr, src, reducer)
@@ -975,7 +1086,10 @@ class HipBackend(object):
         a = self.copy(a)
       if b.stride(1) != 1:
         b = self.copy(b)
-      return self._gemm(a, b, c)
+      pa = pb = None
+      if self._split_tier_takes(a, b):
+        pa, pb = self._gemm_images.operand(a, 0), self._gemm_images.operand(b, 1)
+      return self._gemm(a, b, c, prepared_a=pa, prepared_b=pb)
     va = lower.V('tensor', dtype=a_dt, shape=tuple(a.shape), tensor=self.contiguous(a))
     vb = lower.V('tensor', dtype=b_dt, shape=tuple(b.shape), tensor=self.contiguous(b))
     if a.dim() == 2 and b.dim() == 1:      # (M,K).(K,) -> (M,): row kernels
@@ -997,22 +1111,39 @@ class HipBackend(object):
       return self._run_reduce(prod, 'SUM', res_dt, (M, K, N), 1)
     raise lower.NotLowerable('dot of %d-d and %d-d operands' % (a.dim(), b.dim()))
 
-  def _gemm(self, a, b, c, accumulate=False):
+  def _split_tier_takes(self, a, b):
+    """Does the product a . b run on the split tier with operands that can be cut ahead of it (kernels.gemm_prepare)?"""
+    return (self.dtype_of(a) == np.float32 and kernels.gemm_preparable(a, 0) and kernels.gemm_preparable(b, 1)
+            and kernels.gemm_takes_split(a.shape[0], b.shape[1], a.shape[1]))
+
+  def gemm_images_for(self, x, side, others):
+    """The images of `x` (side 0: the left operand, 1: the right one) for the products with each of `others` on the
+    other side -- cut once, counted in gemm_image_stats -- or None where none of those products would use them.  The
+    caller owns the handle (gemm_into's prepared_a / prepared_b, .view(r0, r1) for a row / column block) and drops it
+    before `x` is written; nothing is cached."""
+    if not any(self._split_tier_takes(*((x, o) if side == 0 else (o, x))) for o in others):
+      return None
+    self._gemm_images.stats['cuts'] += 1
+    return kernels.gemm_prepare(x, side)
+
+  def _gemm(self, a, b, c, accumulate=False, prepared_a=None, prepared_b=None):
     """One sp_gemm launch, c (+)= a . b, between two events when `gemm_events` is a list."""
     self.launches += 1
     if self.gemm_events is None:
-      return kernels.gemm_f32(a, b, c, accumulate=accumulate)
+      return kernels.gemm_f32(a, b, c, accumulate=accumulate, prepared_a=prepared_a, prepared_b=prepared_b)
     e0, e1 = kernels.Event(), kernels.Event()
     e0.record()
-    kernels.gemm_f32(a, b, c, accumulate=accumulate)
+    kernels.gemm_f32(a, b, c, accumulate=accumulate, prepared_a=prepared_a, prepared_b=prepared_b)
     self.gemm_events.append((e0, e1.record(), a.shape[0], b.shape[1], a.shape[1]))      # (start, stop, M, N, K)
     return c
 
-  def gemm_into(self, a, b, out, accumulate=False):
+  def gemm_into(self, a, b, out, accumulate=False, prepared_a=None, prepared_b=None):
     """out (+)= a . b for 2-D fp32 / fp64 tensors that may be strided views (inner stride 1): the building block
-    of the pipelined joins (dot.ksplit_plan), one sp_gemm launch, nothing allocated."""
+    of the pipelined joins (dot.ksplit_plan), one sp_gemm launch, nothing allocated.  prepared_a / prepared_b:
+    gemm_prepare's handle for that operand (a view of it for a block), or None."""
     self.gemms += 1
-    return self._gemm(a, b, out, accumulate)
+    self._wrote(out)
+    return self._gemm(a, b, out, accumulate, prepared_a, prepared_b)
 
   def dot_chunked(self, a, rhs):
     """a . B with B arriving as column chunks (distarray.ChunkedWhole): one GEMM per chunk into the
@@ -1027,9 +1158,12 @@ class HipBackend(object):
     if a.stride(1) != 1:
       a = self.copy(a)
     c = self.empty((a.shape[0], rhs.shape[1]), rhs.dtype)
+    pa = None
     for i in range(len(rhs.chunks)):
       c0, c1, t = rhs.ready(i)
-      self._gemm(a, t, c[:, c0:c1])
+      if i == 0 and len(rhs.chunks) > 1 and t.stride(1) == 1:
+        pa = self.gemm_images_for(a, 0, (t,))       # every chunk multiplies the same a: cut it once
+      self._gemm(a, t, c[:, c0:c1], prepared_a=pa)
     return c
 
   # -- k-means tile bodies (examples/sklearn/cluster/k_means_.py) ---------------------
@@ -1554,6 +1688,7 @@ class HipBackend(object):
   def sparse_scatter(self, dst, ul, blob, mode, mask):
     self.launches += 1
     blob = self.sparse_blob(blob, self.dtype_of(dst))
+    self._wrote(dst)
     sparse_mod.scatter(blob, dst, ul[0], ul[1], mode, mask)
 
   def sparse_to_dense(self, b):

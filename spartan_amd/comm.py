@@ -87,6 +87,13 @@ def _need_dense(*tensors):
       raise AssertionError('a collective was handed a strided view of shape %s: make it contiguous first' % (tuple(t.shape),))
 
 
+def _note_writes(tensors):
+  """These arrays are about to be written by a transfer (devarray.note_write: what was derived from their bytes is void)."""
+  from . import devarray
+  for t in tensors:
+    devarray.note_write(t)
+
+
 def gpu_count():
   """HIP devices visible to libspartan_hip.so (0 when the library is not built or no device answers)."""
   try:
@@ -609,6 +616,7 @@ class World(object):
     for _, t in sends:
       self.stats['p2p_bytes'] += t.nbytes
       self.stats['p2p_msgs'] += 1
+    _note_writes(t for _, t in recvs)
     self.transport.exchange(sends, recvs)
 
   def exchange_async(self, sends, recvs):
@@ -619,6 +627,7 @@ class World(object):
     for _, t in sends:
       self.stats['p2p_bytes'] += t.nbytes
       self.stats['p2p_msgs'] += 1
+    _note_writes(t for _, t in recvs)
     return self.transport.exchange(sends, recvs, async_=True)
 
   def _count(self, nbytes):
@@ -627,6 +636,7 @@ class World(object):
 
   def all_gather_into(self, out, tensor):
     _need_dense(out, tensor)
+    _note_writes((out,))
     self._count(tensor.nbytes * (self.size - 1))
     self.transport.all_gather_into(out, tensor)
 
@@ -635,32 +645,38 @@ class World(object):
     result (the collective runs on a communication stream, so kernels launched meanwhile overlap with it).
     Host-side transports complete immediately and return None."""
     _need_dense(out, tensor)
+    _note_writes((out,))
     self._count(tensor.nbytes * (self.size - 1))
     return self.transport.all_gather_into(out, tensor, async_=True)
 
   def reduce_scatter(self, out, inp, reducer):
     """out[rank piece] = reduce over ranks of inp (inp = size equal pieces)."""
     _need_dense(out, inp)
+    _note_writes((out,))
     self._count(inp.nbytes * (self.size - 1) // self.size)
     self.transport.reduce_scatter(out, inp, reducer)
 
   def reduce_scatter_async(self, out, inp, reducer):
     _need_dense(out, inp)
+    _note_writes((out,))
     self._count(inp.nbytes * (self.size - 1) // self.size)
     return self.transport.reduce_scatter(out, inp, reducer, async_=True)
 
   def all_reduce(self, tensor, reducer):
     _need_dense(tensor)
+    _note_writes((tensor,))
     self._count(2 * tensor.nbytes * (self.size - 1) // self.size)
     self.transport.all_reduce(tensor, reducer)
 
   def reduce(self, tensor, dst, reducer):
     _need_dense(tensor)
+    _note_writes((tensor,))
     self._count(tensor.nbytes)
     self.transport.reduce(tensor, dst, reducer)
 
   def broadcast(self, tensor, src):
     _need_dense(tensor)
+    _note_writes((tensor,))
     self._count(tensor.nbytes)
     self.transport.broadcast(tensor, src)
 

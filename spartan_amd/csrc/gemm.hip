@@ -944,20 +944,69 @@ extern "C" size_t sp_gemm_workspace_bytes(int32_t dtype, int64_t M, int64_t N, i
 extern "C" int sp_gemm_f64(const double*, int64_t, const double*, int64_t, double*, int64_t, int64_t, int64_t, int64_t,
                            int32_t, void*);
 
+extern "C" size_t sp_gemm_image_bytes(int32_t dtype, int32_t side, int64_t rows, int64_t K) {
+  if (dtype != SP_F32 || (side != 0 && side != 1) || rows < 1 || K < 1 || rows > 2147483647LL || K > 2147483647LL) return 0;
+  return sp_gemm_bf16_image_bytes(rows, K);
+}
+
+// The layout the split tier asks of a raw operand (side 0: A [rows][K], side 1: B [K][rows]): what its cut pass and the
+// gated fp32 kernel's direct-to-LDS loads read.
+static bool sp_gemm_bf16_operand_ok(int side, const void* X, int64_t ld, int64_t rows, int64_t K) {
+  return X && ld >= (side == 0 ? K : rows) && ld % 4 == 0 && (((uintptr_t)X) & 15) == 0 &&
+         (int64_t)(side == 0 ? 256 : 16) * ld < (1LL << 30);
+}
+
+extern "C" int64_t sp_gemm_cut_launches(void) { return (int64_t)__atomic_load_n(&gs_cut_launches, __ATOMIC_RELAXED); }
+
+extern "C" int sp_gemm_cut(int32_t side, const void* d_X, int64_t ld, int64_t rows, int64_t K, void* d_img,
+                           size_t img_bytes, void* stream) {
+  if (side != 0 && side != 1) SP_FAIL("sp_gemm_cut: side must be 0 (A) or 1 (B)");
+  const size_t need = sp_gemm_image_bytes(SP_F32, side, rows, K);
+  if (!need) SP_FAIL("sp_gemm_cut: rows and K must be in 1 .. 2^31 - 1");
+  if (!sp_gemm_bf16_operand_ok(side, d_X, ld, rows, K))
+    SP_FAIL("sp_gemm_cut: the operand does not meet the split tier's layout (16-byte aligned, ld % 4 == 0)");
+  if (!d_img || (((uintptr_t)d_img) & 255) != 0 || img_bytes < need)
+    SP_FAIL("sp_gemm_cut: the image buffer must be 256-byte aligned and hold sp_gemm_image_bytes(...) bytes");
+  hipStream_t st = (hipStream_t)stream;
+  SP_HIP(hipMemsetAsync(d_img, 0, GS_IMG_HEAD, st));
+  sp_gemm_bf16_cut(side, (const float*)d_X, ld, rows, K, (char*)d_img + GS_IMG_HEAD, (unsigned*)d_img, st);
+  SP_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int sp_gemm_ws(int32_t dtype, const void* d_A, int64_t lda, const void* d_B, int64_t ldb, void* d_C,
                           int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t accumulate, void* d_ws,
                           size_t ws_bytes, void* stream) {
+  return sp_gemm_ws_images(dtype, d_A, lda, nullptr, 0, 0, d_B, ldb, nullptr, 0, 0, d_C, ldc, M, N, K, accumulate, d_ws,
+                           ws_bytes, stream);
+}
+
+extern "C" int sp_gemm_ws_images(int32_t dtype, const void* d_A, int64_t lda, const void* d_imgA, int64_t a_img_rows,
+                                 int64_t a_row0, const void* d_B, int64_t ldb, const void* d_imgB, int64_t b_img_rows,
+                                 int64_t b_row0, void* d_C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                                 int32_t accumulate, void* d_ws, size_t ws_bytes, void* stream) {
   if (dtype != SP_F32 && dtype != SP_F64) SP_FAIL("sp_gemm_ws: dtype must be f32 or f64");
+  if (d_imgA && (dtype != SP_F32 || (((uintptr_t)d_imgA) & 255) != 0 || a_row0 < 0 || M < 1 || a_row0 + M > a_img_rows))
+    SP_FAIL("sp_gemm_ws_images: A's images must be an fp32 operand's 256-byte aligned buffer that holds rows [row0, row0 + M)");
+  if (d_imgB && (dtype != SP_F32 || (((uintptr_t)d_imgB) & 255) != 0 || b_row0 < 0 || N < 1 || b_row0 + N > b_img_rows))
+    SP_FAIL("sp_gemm_ws_images: B's images must be an fp32 operand's 256-byte aligned buffer that holds columns [row0, row0 + N)");
   const SplitPlan pl = (M > 0 && N > 0) ? sp_split_plan(M, N, K, dtype == SP_F32 ? 16 : 8) : SplitPlan{1, 0};
   const size_t need = sp_gemm_workspace_bytes(dtype, M, N, K);
   // the split tier (gemm_split.hpp): the direct-to-LDS preconditions of sp_gemm_f32's 256 x 128 kernel, which is its
-  // fallback, plus a C the epilogue can address the same way; anything else is the fp32 tier's
+  // fallback, plus a C the epilogue can address the same way; anything else is the fp32 tier's.  The plan and the raw
+  // operands' layout decide, never whether images came with them: the workspace only has to hold the images that
+  // did not (one head, and the three images of each operand cut here)
   const bool bf16x3 = dtype == SP_F32 && pl.splits <= 1 && M > 0 && N > 0 && sp_gemm_bf16_plan(M, N, K);
-  if (bf16x3 && d_ws && ws_bytes >= sp_gemm_bf16_ws_bytes(M, N, K) && d_A && d_B && d_C && lda >= K && ldb >= N && ldc >= N && lda % 4 == 0 &&
-      ldb % 4 == 0 && ((((uintptr_t)d_A) | ((uintptr_t)d_B)) & 15) == 0 && (int64_t)256 * lda < (1LL << 30) &&
-      (int64_t)16 * ldb < (1LL << 30))
-    return sp_gemm_bf16_launch((const float*)d_A, lda, (const float*)d_B, ldb, (float*)d_C, ldc, M, N, K, accumulate,
-                               d_ws, (hipStream_t)stream);
+  if (bf16x3) {
+    const size_t ws_need = (d_imgA && d_imgB) ? 0
+                                              : GS_WS_HEAD + (d_imgA ? 0 : sp_gemm_bf16_image_bytes(M, K) - GS_IMG_HEAD) +
+                                                    (d_imgB ? 0 : sp_gemm_bf16_image_bytes(N, K) - GS_IMG_HEAD);
+    if ((ws_need == 0 || (d_ws && ws_bytes >= ws_need)) && d_C && ldc >= N && sp_gemm_bf16_operand_ok(0, d_A, lda, M, K) &&
+        sp_gemm_bf16_operand_ok(1, d_B, ldb, N, K))
+      return sp_gemm_bf16_launch((const float*)d_A, lda, (const char*)d_imgA, a_img_rows, a_row0, (const float*)d_B, ldb,
+                                 (const char*)d_imgB, b_img_rows, b_row0, (float*)d_C, ldc, M, N, K, accumulate, d_ws,
+                                 (hipStream_t)stream);
+  }
   if (bf16x3)   // (no workspace, or operands the tier does not take)
     return sp_gemm_f32((const float*)d_A, lda, (const float*)d_B, ldb, (float*)d_C, ldc, M, N, K, accumulate, stream);
   if (pl.splits <= 1 && need && d_ws && ws_bytes >= need && dtype == SP_F32 && d_A && d_B && d_C && lda >= K &&

@@ -43,7 +43,9 @@
 // IMAGES.  One pass per operand writes its three bf16 images k-tile-major, [K / 16][rows][16] (the layout
 // sp_split_rows_kernel in kmeans_split.hpp documents: the k-tile of the rows a workgroup brings per k-step is one
 // contiguous block), K padded to 16 with zeros.  A [M][K] is cut as it lies; B [K][N] must be k-contiguous per column,
-// so its pass transposes a 16 x 256 block through LDS.  Nothing is kept between calls: every call cuts its operands.
+// so its pass transposes a 16 x 256 block through LDS.  sp_gemm_ws keeps nothing between calls: every call cuts its
+// operands into its workspace.  A caller that multiplies the same operand again cuts it once into a buffer of its own
+// (sp_gemm_cut) and hands that to sp_gemm_ws_images; the images, the mainloop and so the bits are the same either way.
 // Shapes whose images would not fit under GS_IMAGE_CAP stay on the fp32 tier (cutting K into slabs that accumulate
 // into C is not built: 32768^3 would need seven).
 //
@@ -179,15 +181,18 @@ __global__ __launch_bounds__(256) void sp_gemm_cut_cols_kernel(const float* __re
   gs_raise(bad, flag);
 }
 
-// The mainloop.  Ah / Bh: the hi images, mid and lo `a_img` / `b_img` BYTES behind; KT k-tiles.
+// The mainloop.  Ah / Bh: the hi images, mid and lo `a_img` / `b_img` BYTES behind; KT k-tiles, `a_slab` / `b_slab` bytes
+// apart in an image: 32 x the rows the image was cut with, which is M / N, or more when Ah / Bh point at a row block of
+// the images of a larger operand.  flag_a / flag_b: the window flag of either operand's cut (they may be one word).
 template <int WN>
 __global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf16x3(
     const char* __restrict__ Ah, int64_t a_img, const char* __restrict__ Bh, int64_t b_img, float* __restrict__ C,
-    int64_t ldc, int M, int N, int KT, int accumulate, int tiles_m, int tiles_n, const unsigned* __restrict__ flag) {
+    int64_t ldc, int M, int N, int KT, int accumulate, int tiles_m, int tiles_n, int64_t a_slab, int64_t b_slab,
+    const unsigned* __restrict__ flag_a, const unsigned* __restrict__ flag_b) {
   using G = GsCfg<WN>;
   constexpr int APW = G::APW, BPW = G::BPW, NPIECES = G::NPIECES;
   extern __shared__ __attribute__((aligned(16))) char gs_smem[];
-  if (*flag != 0u) return;                                   // an operand left the window: the gated fp32 launch computes C
+  if ((*flag_a | *flag_b) != 0u) return;                     // an operand left the window: the gated fp32 launch computes C
   int tm, tn;
   sp_gemm_tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n, tm, tn);
   const int m0 = tm * G::BM, n0 = tn * G::BN;
@@ -217,7 +222,6 @@ __global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf1
   }
   const char* __restrict__ Ablk = Ah + (int64_t)m0 * GS_RB;
   const char* __restrict__ Bblk = Bh + (int64_t)n0 * GS_RB;
-  const int64_t a_slab = (int64_t)M * GS_RB, b_slab = (int64_t)N * GS_RB;     // bytes per k-tile of an image
   const unsigned s_base = SP_LDS_ADDR(gs_smem);
 
   // piece i of the request for k-tile kt_ into stage st_: image i / (APW or BPW) of A, then of B
@@ -313,8 +317,9 @@ __global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf1
 template <typename Cfg, int BM, int BN, int WM, int WN, int WGS>
 __global__ __launch_bounds__(Cfg::THREADS, WGS) void sp_gemm_f32_gated_kernel(
     const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, float* __restrict__ C,
-    int64_t ldc, int M, int N, int K, int accumulate, int tiles_m, int tiles_n, const unsigned* __restrict__ flag) {
-  if (*flag == 0u) return;
+    int64_t ldc, int M, int N, int K, int accumulate, int tiles_m, int tiles_n, const unsigned* __restrict__ flag_a,
+    const unsigned* __restrict__ flag_b) {
+  if ((*flag_a | *flag_b) == 0u) return;
   sp_gemm_glds_body<Cfg, BM, BN, WM, WN>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, tiles_m, tiles_n);
 }
 
@@ -354,15 +359,39 @@ static size_t sp_gemm_bf16_ws_bytes(int64_t M, int64_t N, int64_t K) {
   return GS_WS_HEAD + (size_t)((K + GS_BK - 1) / GS_BK) * 3 * GS_RB * (size_t)(M + N);
 }
 
-static int sp_gemm_bf16_launch(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
-                               int64_t N, int64_t K, int acc, void* ws, hipStream_t st) {
-  using G = GsCfg<GS_WN>;
-  char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  unsigned* flag = (unsigned*)base;
+// ---- one operand's images -----------------------------------------------------------------------------------------
+// An image buffer: a 256-byte head whose first word is the operand's own window flag, then the three images
+// [ceil(K / 16)][rows][16] bf16.  The workspace of a call that cuts its operands itself holds the same thing twice over:
+// one head (both cuts raise its one flag), A's images, B's images.
+constexpr size_t GS_IMG_HEAD = 256;
+
+static size_t sp_gemm_bf16_image_bytes(int64_t rows, int64_t K) {
+  return GS_IMG_HEAD + (size_t)((K + GS_BK - 1) / GS_BK) * 3 * GS_RB * (size_t)rows;
+}
+
+static long long gs_cut_launches = 0;      // cut kernels launched by this process (sp_gemm_cut_launches: what the tests count)
+
+// Cut X (side 0: A [rows][K]; side 1: B [K][rows]) into the images at `img`, `img_stride` bytes apart, raising `flag`.
+static void sp_gemm_bf16_cut(int side, const float* X, int64_t ld, int64_t rows, int64_t K, char* img, unsigned* flag,
+                             hipStream_t st) {
   const int64_t KT = (K + GS_BK - 1) / GS_BK;
-  const int64_t a_img = KT * M * GS_RB, b_img = KT * N * GS_RB;       // bytes
-  char* Aimg = base + 256;
-  char* Bimg = Aimg + 3 * a_img;
+  const int64_t img_stride = KT * rows * GS_RB;                        // bytes
+  __atomic_add_fetch(&gs_cut_launches, 1, __ATOMIC_RELAXED);
+  if (side == 0)
+    hipLaunchKernelGGL(sp_gemm_cut_rows_kernel, dim3((unsigned)((rows + 31) / 32), (unsigned)((K + 255) / 256)), dim3(256), 0,
+                       st, X, ld, (int)rows, (int)K, (__bf16*)img, img_stride / 2, flag);
+  else
+    hipLaunchKernelGGL(sp_gemm_cut_cols_kernel, dim3((unsigned)((rows + 255) / 256), (unsigned)KT), dim3(256), 0, st, X, ld,
+                       (int)rows, (int)K, (__bf16*)img, img_stride / 2, flag);
+}
+
+// The multiply.  imgA / imgB: an operand's image buffer (head first) cut with a_rows / b_rows rows, of which this
+// product takes rows [a_row0, a_row0 + M) / [b_row0, b_row0 + N) -- or null: that operand is cut into `ws` here.
+static int sp_gemm_bf16_launch(const float* A, int64_t lda, const char* imgA, int64_t a_rows, int64_t a_row0,
+                               const float* B, int64_t ldb, const char* imgB, int64_t b_rows, int64_t b_row0, float* C,
+                               int64_t ldc, int64_t M, int64_t N, int64_t K, int acc, void* ws, hipStream_t st) {
+  using G = GsCfg<GS_WN>;
+  const int64_t KT = (K + GS_BK - 1) / GS_BK;
   const int64_t tiles_m = (M + G::BM - 1) / G::BM, tiles_n = (N + G::BN - 1) / G::BN;
   auto kern = sp_gemm_glds_kernel_bf16x3<GS_WN>;
   using FCfg = GldsCfg<256, 128, 2, 2>;
@@ -373,17 +402,33 @@ static int sp_gemm_bf16_launch(const float* A, int64_t lda, const float* B, int6
     SP_HIP(hipFuncSetAttribute((const void*)gated, hipFuncAttributeMaxDynamicSharedMemorySize, FCfg::LDS_BYTES));
     attr_set = true;
   }
-  SP_HIP(hipMemsetAsync(flag, 0, 256, st));
-  hipLaunchKernelGGL(sp_gemm_cut_rows_kernel, dim3((unsigned)((M + 31) / 32), (unsigned)((K + 255) / 256)), dim3(256), 0, st,
-                     A, lda, (int)M, (int)K, (__bf16*)Aimg, a_img / 2, flag);
-  hipLaunchKernelGGL(sp_gemm_cut_cols_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)KT), dim3(256), 0, st, B, ldb,
-                     (int)N, (int)K, (__bf16*)Bimg, b_img / 2, flag);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(G::THREADS), G::SMEM_BYTES, st, (const char*)Aimg,
-                     a_img, (const char*)Bimg, b_img, C, ldc, (int)M, (int)N, (int)KT, acc, (int)tiles_m, (int)tiles_n,
-                     (const unsigned*)flag);
+  char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);      // (not touched when both operands come cut)
+  char* next = base + GS_IMG_HEAD;
+  if (!imgA || !imgB) SP_HIP(hipMemsetAsync(base, 0, GS_IMG_HEAD, st));
+  const unsigned* flag_a = (const unsigned*)(imgA ? imgA : base);
+  const unsigned* flag_b = (const unsigned*)(imgB ? imgB : base);
+  const char *Ah, *Bh;
+  if (imgA) {
+    Ah = imgA + GS_IMG_HEAD + a_row0 * GS_RB;
+  } else {
+    a_rows = M;
+    sp_gemm_bf16_cut(0, A, lda, M, K, next, (unsigned*)base, st);
+    Ah = next;
+    next += 3 * KT * M * GS_RB;
+  }
+  if (imgB) {
+    Bh = imgB + GS_IMG_HEAD + b_row0 * GS_RB;
+  } else {
+    b_rows = N;
+    sp_gemm_bf16_cut(1, B, ldb, N, K, next, (unsigned*)base, st);
+    Bh = next;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(G::THREADS), G::SMEM_BYTES, st, Ah,
+                     KT * a_rows * GS_RB, Bh, KT * b_rows * GS_RB, C, ldc, (int)M, (int)N, (int)KT, acc, (int)tiles_m,
+                     (int)tiles_n, a_rows * GS_RB, b_rows * GS_RB, flag_a, flag_b);
   const int64_t ftm = (M + 255) / 256, ftn = (N + 127) / 128;
   hipLaunchKernelGGL(gated, dim3((unsigned)(ftm * ftn)), dim3(FCfg::THREADS), FCfg::LDS_BYTES, st, A, lda, B, ldb, C, ldc,
-                     (int)M, (int)N, (int)K, acc, (int)ftm, (int)ftn, (const unsigned*)flag);
+                     (int)M, (int)N, (int)K, acc, (int)ftm, (int)ftn, flag_a, flag_b);
   SP_CHECK_LAUNCH();
   return 0;
 }

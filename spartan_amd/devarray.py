@@ -123,7 +123,7 @@ def synchronize():
 class Storage(object):
   """One allocation of the tile store: a 1-D byte blob (sp_blob_create), given back by sp_blob_destroy when the
   last view of it dies.  The store pools freed allocations by size class and reuses them in stream order."""
-  __slots__ = ('handle', 'ptr', 'nbytes', '__weakref__')
+  __slots__ = ('handle', 'ptr', 'nbytes', 'version', '__weakref__')
   on_device = True
 
   def __init__(self, nbytes):
@@ -133,8 +133,10 @@ class Storage(object):
     p = C.c_void_p()
     check(_hip.lib().sp_blob_info(h, C.byref(p), None, None, None))
     self.handle, self.ptr, self.nbytes = h, int(p.value or 0), nbytes
+    self.version = 0      # note_write: what is derived from the bytes (the backend's GEMM images) records it
 
   def h2d(self, byte_offset, host_ptr, nbytes):
+    self.version += 1
     if nbytes:
       st = current_stream().ptr
       consumed = C.c_int32(0)
@@ -158,19 +160,30 @@ class Storage(object):
 
 class HostStorage(object):
   """Test stand-in for `Storage` in host memory (view arithmetic is checked against NumPy without a GPU)."""
-  __slots__ = ('buf', 'ptr', 'nbytes', '__weakref__')
+  __slots__ = ('buf', 'ptr', 'nbytes', 'version', '__weakref__')
   on_device = False
 
   def __init__(self, nbytes):
     self.buf = np.zeros(max(int(nbytes), 1), np.uint8)
     self.ptr = self.buf.ctypes.data
     self.nbytes = self.buf.nbytes
+    self.version = 0
 
   def h2d(self, byte_offset, host_ptr, nbytes):
+    self.version += 1
     C.memmove(self.ptr + byte_offset, host_ptr, nbytes)
 
   def d2h(self, byte_offset, host_ptr, nbytes):
     C.memmove(host_ptr, self.ptr + byte_offset, nbytes)
+
+
+def note_write(t):
+  """Something is about to write into the existing array `t` (or has just been enqueued to): its storage's version
+  moves on, so that nothing derived from the old bytes is taken for the new ones (HipBackend's GEMM image cache).  Every
+  path that writes into an array it did not allocate itself calls this; DESIGN.md has the list."""
+  s = getattr(t, 'storage', None)
+  if type(s) is Storage or type(s) is HostStorage:
+    s.version += 1
 
 
 def blob_stats():
@@ -180,8 +193,24 @@ def blob_stats():
   return live.value, pooled.value
 
 
+_trim_hooks = []
+
+
+def on_trim(method):
+  """Call the bound method `method` (held weakly) at the start of every trim_pool(): for whoever keeps device memory
+  that is only a cache (the backend's GEMM images)."""
+  _trim_hooks.append(weakref.WeakMethod(method))
+
+
 def trim_pool():
-  """Give the pooled (free) allocations back to the driver."""
+  """Give the pooled (free) allocations back to the driver, and before that what the caches registered with on_trim
+  hold."""
+  for ref in list(_trim_hooks):
+    method = ref()
+    if method is None:
+      _trim_hooks.remove(ref)
+    else:
+      method()
   check(_hip.lib().sp_blob_trim())
 
 
@@ -500,6 +529,7 @@ class DevArray(object):
     HIP devices are exposed to those libraries under this name as well."""
     if not self.storage.on_device:
       raise AttributeError('not a device array')
+    self.storage.version = -1 << 62      # another library may write these bytes unseen: never taken as unchanged again
     item = self.dtype.itemsize
     return {'shape': self.shape, 'typestr': self.dtype.str, 'data': (self.data_ptr(), False), 'version': 3,
             'strides': None if self.is_contiguous() else tuple(s * item for s in self.strides)}

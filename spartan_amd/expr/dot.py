@@ -198,7 +198,7 @@ def ksplit_plan(arrays, axes, target, fn_kw):
   return True
 
 
-def ksplit_pipeline(be, p, me, my_a, my_b, dt, exchange_async, reduce_scatter_async, nc):
+def ksplit_pipeline(be, p, me, my_a, my_b, dt, exchange_async, reduce_scatter_async, nc, prepare=True):
   """One rank's share of the K-split dot: my row tile of a (m/p x k), my rows of b (k/p x n) -> my row tile of the
   result (m/p x n).  `exchange_async(sends, recvs)` / `reduce_scatter_async(out, part)` are the transport's
   (World's on a real job; bench.py --emulate-rank substitutes same-size device copies on a side stream to time a
@@ -211,7 +211,13 @@ def ksplit_pipeline(be, p, me, my_a, my_b, dt, exchange_async, reduce_scatter_as
        later chunk is ONE GEMM slab . b[:, chunk] -- (m x k/p) . (k/p x nc), thousands of macro-tiles per launch
        instead of p launches of one partly filled round each;
     3. each finished chunk is reduce-scattered asynchronously while the next one is multiplied; the reduced
-       pieces are pasted into the result as they land.  Only the last chunk's reduce-scatter is exposed."""
+       pieces are pasted into the result as they land.  Only the last chunk's reduce-scatter is exposed.
+
+  Every chunk multiplies the same slab, so (prepare=True, and where the backend's GEMM has operand images at all:
+  HipBackend.gemm_images_for) the slab is cut into its split-tier images ONCE, when its blocks have landed: the two
+  row-block products of chunk 0 take row views of them, every later chunk the whole.  Chunk 0's b_chunk is cut once
+  for its three products.  The bits are those of prepare=False, which cuts inside every product."""
+  prep = getattr(be, 'gemm_images_for', None) if prepare else None
   mb, k = my_a.shape
   kb = k // p
   n = my_b.shape[1]
@@ -237,14 +243,21 @@ def ksplit_pipeline(be, p, me, my_a, my_b, dt, exchange_async, reduce_scatter_as
     part = bufs[ci % 2]
     b_chunk = my_b[:, c0:c0 + nc]
     if ci == 0:
-      be.gemm_into(slab[rows(me, me + 1), :], b_chunk, part[rows(me, me + 1), :])     # needs no transfer
+      blocks = [(j0, j1) for j0, j1 in ((0, me), (me + 1, p)) if j1 > j0]
+      lhs = [slab[rows(j0, j1), :] for j0, j1 in [(me, me + 1)] + blocks]
+      kw = {'prepared_b': prep(b_chunk, 1, lhs)} if prep else {}
+      be.gemm_into(lhs[0], b_chunk, part[rows(me, me + 1), :], **kw)     # needs no transfer
       if arriving is not None:
         arriving.wait()
-      for j0, j1 in ((0, me), (me + 1, p)):
-        if j1 > j0:
-          be.gemm_into(slab[rows(j0, j1), :], b_chunk, part[rows(j0, j1), :])
+      slab_images = None
+      if prep and nc < n:      # for the whole-slab products of the later chunks, and the row blocks of this one
+        slab_images = prep(slab, 0, [my_b[:, nc:2 * nc]])
+      for (j0, j1), x in zip(blocks, lhs[1:]):
+        if slab_images is not None:
+          kw['prepared_a'] = slab_images.view(j0 * mb, j1 * mb)
+        be.gemm_into(x, b_chunk, part[rows(j0, j1), :], **kw)
     else:
-      be.gemm_into(slab, b_chunk, part)
+      be.gemm_into(slab, b_chunk, part, **({'prepared_a': slab_images} if slab_images is not None else {}))
     piece = be.empty((mb, nc), dt)
     handle = reduce_scatter_async(piece, part)
     if in_flight is not None:

@@ -5,6 +5,8 @@ that can say where its bytes live in HBM -- `data_ptr()`, `shape`, `stride()`, `
 a test may hand in memory from another allocator.  Launches go to devarray.current_stream().  No torch here.
 """
 import ctypes as C
+import functools
+import inspect
 
 import numpy as np
 
@@ -46,6 +48,26 @@ def _p(t):
   return C.c_void_p(None if t is None else t.data_ptr())
 
 
+def _writes(*names):
+  """Decorator of a launcher whose parameters `names` are arrays the kernel writes: each one that is given has its
+  storage's version moved on (devarray.note_write) before the launch, so that whatever was derived from the old bytes --
+  the backend's GEMM images -- is void whoever calls the launcher.  For an array made a line earlier this is one integer
+  increment."""
+  def deco(fn):
+    params = list(inspect.signature(fn).parameters)
+    where = [(n, params.index(n)) for n in names]
+
+    @functools.wraps(fn)
+    def launcher(*args, **kw):
+      for n, i in where:
+        t = args[i] if i < len(args) else kw.get(n)
+        if t is not None:
+          devarray.note_write(t)
+      return fn(*args, **kw)
+    return launcher
+  return deco
+
+
 def _float_dtype(what, first, *others):
   """The dtype of `first` for a launcher `what` that exists in float32 and float64 only: TypeError for an operand of
   another dtype, or for one of `others` (None is skipped) whose dtype is not that of `first`, in the operands' order."""
@@ -74,6 +96,7 @@ class Workspace(object):
 _ws = Workspace()
 
 
+@_writes('out')
 def map_fused(prog, inputs, out):
   """Launch the fused map `prog` over dense tensors; `out` is written."""
   _require_device(out, *inputs)
@@ -85,6 +108,7 @@ def map_fused(prog, inputs, out):
 _reduce_ws_bytes = {}
 
 
+@_writes('out')
 def reduce(prog, inputs, red_op, outer, axis_len, inner, out):
   _require_device(out, *inputs)
   lib = _hip.lib()
@@ -108,6 +132,7 @@ def reduce_warm(prog, inputs, red_op, outer, axis_len, inner, out_dtype):
   _ws.get(need)
 
 
+@_writes('out_idx', 'out_val')
 def argreduce(prog, inputs, which, outer, axis_len, inner, index_offset, nan_index, out_idx, out_val=None):
   _require_device(out_idx, out_val, *inputs)
   lib = _hip.lib()
@@ -122,6 +147,7 @@ def argreduce(prog, inputs, which, outer, axis_len, inner, index_offset, nan_ind
   return out_idx
 
 
+@_writes('dst')
 def update(dst, ul, lr, src, reducer, mask_mode, mask=None):
   """Tile.merge: dst[ul:lr] = merge(dst[ul:lr], src) with the tile's mask state."""
   _require_device(dst, src, mask)
@@ -134,6 +160,7 @@ def update(dst, ul, lr, src, reducer, mask_mode, mask=None):
   return dst
 
 
+@_writes('dst')
 def slice_copy(dst, dst_offset, dst_strides, src, src_offset, src_strides, shape):
   """Strided box copy between two blobs of the same element size (strides/offsets in elements)."""
   _require_device(dst, src)
@@ -147,8 +174,82 @@ def slice_copy(dst, dst_offset, dst_strides, src, src_offset, src_strides, shape
   return dst
 
 
-def gemm_f32(a, b, c, accumulate=False):
-  """c (+)= a . b for 2-D row-major fp32 (or, all three, fp64) tensors (inner stride 1)."""
+class GemmImages(object):
+  """One fp32 GEMM operand cut into the split tier's bf16 images (gemm_prepare): `buf` holds the operand's own window
+  flag and the three images of all `img_rows` rows; the handle stands for rows [row0, row0 + rows) of them.  `event`
+  was recorded on `stream` behind the cut: a product on another stream waits for it (gemm_f32 does).  The images are
+  a snapshot: whoever keeps a handle across a write into the operand has to cut again."""
+  __slots__ = ('buf', 'side', 'img_rows', 'K', 'row0', 'rows', 'event', 'stream')
+
+  def __init__(self, buf, side, img_rows, K, row0, rows, event, stream):
+    self.buf, self.side, self.img_rows, self.K = buf, side, img_rows, K
+    self.row0, self.rows, self.event, self.stream = row0, rows, event, stream
+
+  nbytes = property(lambda self: self.buf.numel())
+
+  def view(self, r0, r1):
+    """The images of rows [r0, r1) of this handle's operand (side 1: of its columns): nothing is cut again."""
+    r0, r1 = int(r0), int(r1)
+    if not 0 <= r0 < r1 <= self.rows:
+      raise ValueError('rows [%d, %d) of a prepared operand of %d rows' % (r0, r1, self.rows))
+    return GemmImages(self.buf, self.side, self.img_rows, self.K, self.row0 + r0, r1 - r0, self.event, self.stream)
+
+
+def gemm_preparable(x, side):
+  """Can `x` be cut by gemm_prepare: a 2-D fp32 device tensor that meets the split tier's layout for that side?"""
+  if not getattr(x, 'is_cuda', False) or x.dim() != 2 or np_dtype_of(x) != np.float32:
+    return False
+  r, c = x.shape
+  if r < 1 or c < 1 or r > 2147483647 or c > 2147483647 or (c > 1 and x.stride(1) != 1):
+    return False
+  ld = x.stride(0) if r > 1 else c
+  return ld >= c and ld % 4 == 0 and x.data_ptr() % 16 == 0 and (256 if side == 0 else 16) * ld < (1 << 30)
+
+
+def gemm_takes_split(M, N, K):
+  """Does the fp32 product [M][K] . [K][N] run on the split tier (given operands that meet its layout)?"""
+  return _hip.lib().sp_gemm_split_workspace_bytes(_hip.SP_F32, int(M), int(N), int(K)) > 0
+
+
+def gemm_cut_launches():
+  """How many cut kernels (one per operand cut, into a workspace or into a buffer) this process has launched."""
+  return int(_hip.lib().sp_gemm_cut_launches())
+
+
+def gemm_prepare(x, side):
+  """Cut the fp32 operand `x` of a product once -- side 0: the left one, [M][K]; side 1: the right one, [K][N] -- into
+  a buffer of its own (sp_gemm_cut), for any number of gemm_f32(..., prepared_a= / prepared_b=) calls while `x` keeps
+  its bytes.  Returns a GemmImages.  Nothing remembers the handle: the caller owns it."""
+  if side not in (0, 1) or not gemm_preparable(x, side):
+    raise ValueError('gemm_prepare: side %r of a %s %s tensor with strides %s cannot be cut'
+                     % (side, tuple(x.shape), x.dtype, tuple(x.stride())))
+  lib = _hip.lib()
+  rows, K = (x.shape[0], x.shape[1]) if side == 0 else (x.shape[1], x.shape[0])
+  nbytes = lib.sp_gemm_image_bytes(_hip.SP_F32, side, rows, K)
+  buf = devarray.empty((nbytes,), np.uint8)
+  check(lib.sp_gemm_cut(side, _p(x), x.stride(0) if x.shape[0] > 1 else x.shape[1], rows, K, _p(buf), nbytes, _stream()))
+  stream = devarray.current_stream()
+  return GemmImages(buf, side, rows, K, 0, rows, Event().record(stream), stream)
+
+
+def _prepared(h, side, rows, K, dt):
+  """The (buffer, rows it was cut with, first row taken) arguments of a prepared operand; (NULL, 0, 0) for None."""
+  if h is None:
+    return C.c_void_p(0), 0, 0
+  if dt != _hip.SP_F32 or h.side != side or h.rows != rows or h.K != K:
+    raise ValueError('gemm_f32: the prepared operand (side %d, %d x %d) is not side %d of this fp32 product (%d x %d)'
+                     % (h.side, h.rows, h.K, side, rows, K))
+  if h.stream is not devarray.current_stream():
+    devarray.current_stream().wait_event(h.event)
+  return C.c_void_p(h.buf.data_ptr()), h.img_rows, h.row0
+
+
+@_writes('c')
+def gemm_f32(a, b, c, accumulate=False, prepared_a=None, prepared_b=None):
+  """c (+)= a . b for 2-D row-major fp32 (or, all three, fp64) tensors (inner stride 1).  prepared_a / prepared_b:
+  gemm_prepare's handle of `a` / `b` (or a view() of one for a row block of a / a column block of b): where the
+  split tier runs, that operand is not cut again; where it does not, the handle is ignored.  The bits do not depend on
+  it.  Nothing is cached here: without a handle every call cuts."""
   _require_device(a, b, c)
   adt = np_dtype_of(a)
   assert adt == np_dtype_of(b) == np_dtype_of(c) and adt in (np.float32, np.float64)
@@ -158,14 +259,20 @@ def gemm_f32(a, b, c, accumulate=False):
   K2, N = b.shape
   assert K == K2 and tuple(c.shape) == (M, N), (a.shape, b.shape, c.shape)
   assert a.stride(1) == 1 and b.stride(1) == 1 and c.stride(1) == 1
-  need = max(lib.sp_gemm_workspace_bytes(dt, M, N, K),         # > 0: few output tiles, long contraction -> split-K
-             lib.sp_gemm_split_workspace_bytes(dt, M, N, K))   # > 0: the operand images of the bf16 split tier
+  pa, a_rows, a_row0 = _prepared(prepared_a, 0, M, K, dt)
+  pb, b_rows, b_row0 = _prepared(prepared_b, 1, N, K, dt)
+  need = lib.sp_gemm_workspace_bytes(dt, M, N, K)         # > 0: few output tiles, long contraction -> split-K
+  if prepared_a is None and prepared_b is None:
+    need = max(need, lib.sp_gemm_split_workspace_bytes(dt, M, N, K))   # > 0: the operand images of the bf16 split tier
+  elif lib.sp_gemm_split_workspace_bytes(dt, M, N, K):    # the head, and the images of the side that comes raw
+    need = max(need, 512 + sum(lib.sp_gemm_image_bytes(dt, side, rows, K) - 256
+                               for side, rows, h in ((0, M, prepared_a), (1, N, prepared_b)) if h is None))
   ws = _ws.get(need, a.device) if need else None
-  check(lib.sp_gemm_ws(dt, C.c_void_p(a.data_ptr()), a.stride(0) if M > 1 else max(K, 1),
-                       C.c_void_p(b.data_ptr()), b.stride(0) if K > 1 else max(N, 1),
-                       C.c_void_p(c.data_ptr()), c.stride(0) if M > 1 else max(N, 1),
-                       M, N, K, 1 if accumulate else 0, C.c_void_p(ws.data_ptr() if need else 0),
-                       ws.numel() if need else 0, _stream()))
+  check(lib.sp_gemm_ws_images(dt, C.c_void_p(a.data_ptr()), a.stride(0) if M > 1 else max(K, 1), pa, a_rows, a_row0,
+                              C.c_void_p(b.data_ptr()), b.stride(0) if K > 1 else max(N, 1), pb, b_rows, b_row0,
+                              C.c_void_p(c.data_ptr()), c.stride(0) if M > 1 else max(N, 1),
+                              M, N, K, 1 if accumulate else 0, C.c_void_p(ws.data_ptr() if need else 0),
+                              ws.numel() if need else 0, _stream()))
   return c
 
 
@@ -181,6 +288,7 @@ def _rowdot_operands(x, w, y, out):
   return n, d, ldx, (y.stride(0) if y is not None and n > 1 else 1), _ws.get(need, x.device)
 
 
+@_writes('out')
 def rowdot_colsum(x, w, y, out, accumulate=False):
   """out[c] (+)= sum_i x[i, c] * (x[i, :] . w - y[i]) in one pass over the fp32 row tile x [n, d] (y may be None);
   False when the operands do not meet sp_rowdot_colsum_f32's layout (the caller then takes the two-launch form)."""
@@ -193,6 +301,7 @@ def rowdot_colsum(x, w, y, out, accumulate=False):
   return True
 
 
+@_writes('out')
 def rowdot_link_colsum(x, w, y, out, link, accumulate=False):
   """out[c] (+)= sum_i x[i, c] * (link(x[i, :] . w) - y[i]) in one pass over the fp32 row tile x [n, d] (y may be None),
   link one of _hip.SP_LINK_*: sp_rowdot_link_colsum_f32.  False when the operands do not meet the kernel's layout
@@ -228,6 +337,7 @@ def prepare_points(points):
   return out
 
 
+@_writes('labels')
 def nearest_center(points, centers, labels, tier=_hip.NEAREST_AUTO, prepared=None):
   """labels[i] = argmin_c |points[i] - centers[c]| (cdist + argmin; k_means_.py:61-66)."""
   _require_device(points, centers, labels)
@@ -252,6 +362,7 @@ def nearest_center(points, centers, labels, tier=_hip.NEAREST_AUTO, prepared=Non
   return labels
 
 
+@_writes('counts')
 def bincount(labels, k, counts):
   """counts[:k] = np.bincount(labels, minlength=k) (k_means_.py:69-72)."""
   _require_device(labels, counts)
@@ -262,6 +373,7 @@ def bincount(labels, k, counts):
   return counts
 
 
+@_writes('out', 'counts')
 def segment_sum(points, labels, k, out, counts=None):
   """out[c] = points[labels == c].sum(axis=0) (k_means_.py:75-97); counts (int64 [k], optional) = np.bincount(labels,
   minlength=k): the counting sort inside has the number anyway."""
@@ -284,6 +396,7 @@ def segment_sum(points, labels, k, out, counts=None):
 RANDOM_KINDS = {'uniform': 0, 'normal': 1, 'randint': 2}
 
 
+@_writes('out')
 def random_fill(out, kind, seed, offset, lo=0, hi=1):
   """Philox fill of a dense tensor: element i = f(seed, offset + i) (srandom.py:38-55)."""
   _require_device(out)
@@ -294,6 +407,7 @@ def random_fill(out, kind, seed, offset, lo=0, hi=1):
   return out
 
 
+@_writes('out')
 def cumscan(src, out, axis, product=False):
   """out = np.cumsum / np.cumprod(src, axis) for dense tensors of one dtype (scan.py:42-63)."""
   _require_device(src, out)
@@ -324,6 +438,7 @@ def sort_rows(src, values=True, indices=False):
   return vals, idx
 
 
+@_writes('a', 'info')
 def potrf(a, info):
   """In place: the lower triangle of the square fp32 / fp64 matrix `a` (a view with inner stride 1 will do) becomes
   its Cholesky factor L, the strict upper triangle zero (sp_potrf); `info`, a device int32, receives 0 or the order
@@ -340,6 +455,7 @@ def potrf(a, info):
   return a
 
 
+@_writes('b')
 def trsm_rlt(b, l):
   """In place: b <- x with x . l^T = b, `l` square lower triangular (its upper triangle is not read), `b` [m, n]; both
   fp32 or both fp64, views with inner stride 1 (sp_trsm_rlt)."""
@@ -355,6 +471,7 @@ def trsm_rlt(b, l):
   return b
 
 
+@_writes('w', 'v', 'info')
 def syevj(a, w, v, info):
   """Eigenvalues (ascending, into the vector `w`) and eigenvectors (the columns of `v`, same order) of the symmetric
   fp32 / fp64 matrix `a`, whose lower triangle is read and which is NOT written (sp_syevj: cyclic two-sided Jacobi);
@@ -376,6 +493,7 @@ def syevj(a, w, v, info):
   return int(sweeps.value)
 
 
+@_writes('dist2', 'idx')
 def knn(q, x, k, dist2, idx, index_offset=0, splits=0):
   """dist2[i], idx[i] <- the k rows of `x` [np, d] nearest to row i of `q` [nq, d] by squared Euclidean distance
   (difference form), ascending by (distance, index); idx = index_offset + row of x, padded with +inf / -1 when np < k
@@ -399,6 +517,7 @@ def knn(q, x, k, dist2, idx, index_offset=0, splits=0):
   return dist2, idx
 
 
+@_writes('dist2', 'idx')
 def knn_merge(cand_dist2, cand_idx, k, dist2, idx):
   """dist2[i], idx[i] <- the k smallest by (distance, index) of the m candidates of row i; candidates with a negative
   index are padding (sp_knn_merge).  cand_dist2 (fp32 / fp64) and cand_idx (int64): [nq, m] views with inner stride 1
@@ -416,6 +535,7 @@ def knn_merge(cand_dist2, cand_idx, k, dist2, idx):
   return dist2, idx
 
 
+@_writes('d', 'info')
 def apsp(d, info):
   """In place: the square fp32 / fp64 matrix `d` of edge lengths (>= 0, +inf = no edge, the diagonal taken as 0; a view
   with inner stride 1 will do) becomes the matrix of shortest-path lengths, +inf where there is no path (sp_apsp:
@@ -430,6 +550,7 @@ def apsp(d, info):
   return d
 
 
+@_writes('w')
 def graph_from_knn(dist, idx, w):
   """w [n, n] <- the dense undirected graph of the neighbour lists dist (fp32 / fp64, >= 0) and idx (int64), both [n, k]
   views with inner stride 1 and ONE row stride: +inf, 0 on the diagonal, and for every listed pair (i, idx[i][e]) the
@@ -447,6 +568,7 @@ def graph_from_knn(dist, idx, w):
   return w
 
 
+@_writes('x', 'info')
 def als_solve(r, y, la, alpha, implicit, x, info):
   """x[i] <- the solution of row i's normal equations of one ALS half-step: ratings `r` [m, n], factors `y` [n, f],
   both fp32 or both fp64, views with inner stride 1; `x` [m, f] of their dtype, a view with inner stride 1
@@ -475,6 +597,7 @@ def als_solve(r, y, la, alpha, implicit, x, info):
   return x
 
 
+@_writes('labels', 'sums', 'wsum', 'u')
 def fuzzy_step(points, centers, m, labels, sums, wsum, u=None, splits=0):
   """One iteration of the reference's fuzzy k-means on a row tile (sp_fuzzy_step; include/spartan_hip_fuzzy.h states
   the arithmetic and its order): `points` [n, d] and `centers` [k, d], both fp32 or both fp64, views with inner stride
@@ -524,6 +647,7 @@ def check_lda_params(k, alpha, eta, iters, what='lda_step'):
   return alpha, eta, int(iters)
 
 
+@_writes('delta', 'doc_topics')
 def lda_step(x, n, alpha, eta, iters, delta=None, doc_topics=None, splits=0):
   """One CVB0 step of the reference's LDA on a tile of documents (sp_lda_step; include/spartan_hip_lda.h states the
   arithmetic and its order): `x` [V, D] terms x documents and `n` [k, V] topic / term counts, both fp32 or both fp64,
@@ -562,6 +686,7 @@ def affinity_operands(what, x, y, *others):
   return dt, int(x.shape[0]), int(y.shape[0]), int(x.shape[1])
 
 
+@_writes('deg')
 def affinity_degree(x, y, metric, gamma, deg):
   """deg[i] <- sum_j a(x_i, y_j) over all rows of `y` (sp_affinity_degree; include/spartan_hip_spectral.h states the
   measures and the order of the sum): `x` [m, d] and `y` [n, d], both fp32 or both fp64, views with inner stride 1;
@@ -584,6 +709,7 @@ def affinity_degree(x, y, metric, gamma, deg):
   return deg
 
 
+@_writes('out')
 def affinity_matrix(x, r0, y, metric, gamma, out, scale=None):
   """out[i, j] <- a(x_i, y_j), where row i of `x` [m, d] is point r0 + i of the n points `y` [n, d]; with `scale` [n]
   (contiguous): a_ij * (scale[r0 + i] * scale[j]) and exactly 1 at j = r0 + i (sp_affinity_matrix;
@@ -617,6 +743,7 @@ def gather_rows(src, idx):
   return out
 
 
+@_writes('dst')
 def stream_copy(dst, src, nbytes=None, max_workgroups=0, stream=None):
   """dst <- src (contiguous bytes); max_workgroups > 0 bounds the grid (a transfer that takes a limited share of
   the CUs, see sp_stream_copy_wg)."""

@@ -297,6 +297,7 @@ def spmm(a, b, out=None, accumulate=False, plan=True):
   # both kernels write rows of n consecutive values: a caller's strided `out` (a column of a wider matrix, a view
   # with a step) is computed into a packed buffer and pasted over itself afterwards
   strided_out = None
+  D.note_write(out)      # (an existing array is written in place; None is nothing)
   if out is None:
     out = D.empty((m, n), dtype)
   elif not out.is_contiguous():
@@ -345,6 +346,7 @@ def scatter(t, out, row0=0, col0=0, mode=0, mask=None):
   """Write `t` into the box of the dense 2-D tensor `out` at (row0, col0): mode 0 assign, 1 add,
   2 the reference's masked first-write rule (sparse.pyx:21-38)."""
   assert out.dim() == 2 and out.stride(1) == 1 and np_dtype_of(out) == t.dtype
+  D.note_write(out)
   if t.nnz:
     check(_hip.lib().sp_csr_scatter(_hip.sp_dtype(t.dtype), t.shape[0], t.nnz, _p(t.indptr), _p(t.indices), _p(t.data),
                                     C.c_void_p(out.data_ptr()), out.stride(0) if out.shape[0] > 1 else out.shape[1],
