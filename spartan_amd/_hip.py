@@ -319,6 +319,10 @@ _EXTRAS_ABI = {
         'sp_affinity_matrix': (C.c_int, [_i32, _i32, _f64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64,
                                          _vp]),
     },
+    'spartan_hip_nb.h': {
+        'sp_nb_step': (C.c_int, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+        'sp_nb_step_workspace_bytes': (_sz, [_i32, _i64, _i64, _i64, _i32]),
+    },
 }
 EXPORTS_EXTRAS = list(_EXTRAS_ABI['spartan_hip_extras.h'])
 EXPORTS_EIG = list(_EXTRAS_ABI['spartan_hip_eig.h'])
@@ -328,9 +332,11 @@ EXPORTS_ALS = list(_EXTRAS_ABI['spartan_hip_als.h'])
 EXPORTS_FUZZY = list(_EXTRAS_ABI['spartan_hip_fuzzy.h'])
 EXPORTS_LDA = list(_EXTRAS_ABI['spartan_hip_lda.h'])
 EXPORTS_SPECTRAL = list(_EXTRAS_ABI['spartan_hip_spectral.h'])
+EXPORTS_NB = list(_EXTRAS_ABI['spartan_hip_nb.h'])
 KNN_MAX_K = 128       # SP_KNN_MAX_K of spartan_hip_knn.h
 SP_ALS_MAX_F = 64     # of spartan_hip_als.h
 SP_LDA_MAX_K = 128    # of spartan_hip_lda.h
+SP_NB_MAX_LABELS = 128   # of spartan_hip_nb.h
 SP_AFF_METRICS = {'rbf': 0, 'euclidean': 1, 'manhattan': 2}   # SP_AFF_* of spartan_hip_spectral.h
 
 
@@ -348,12 +354,32 @@ def check_affinity_params(metric, gamma, what='affinity'):
   if gamma != gamma or gamma in (float('inf'), float('-inf')):
     raise ValueError('%s: gamma = %r must be finite' % (what, gamma))
   return SP_AFF_METRICS[metric], gamma
+
+
+def check_nb_operands(x_dtype, x_shape, labels_dtype, labels_shape, label_size, what='nb_step'):
+  """(m, d, label_size) of the operands of a naive Bayes step, or what sp_nb_step refuses: TypeError for data that is
+  not float32 / float64 or labels that are not int64, ValueError for label_size outside 1 .. 128, data that is not 2-D
+  or labels that are not [m] or [m, 1].  The one copy: the launcher, the backend and the NumPy body of examples/_nb.py
+  all refuse through it."""
+  if np.dtype(x_dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+    raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, np.dtype(x_dtype)))
+  if np.dtype(labels_dtype) != np.dtype(np.int64):
+    raise TypeError('%s: labels of dtype %s; convert with astype(int64) first' % (what, np.dtype(labels_dtype)))
+  label_size = int(label_size)
+  if not 1 <= label_size <= SP_NB_MAX_LABELS:
+    raise ValueError('%s: label_size = %d must be in 1 .. %d' % (what, label_size, SP_NB_MAX_LABELS))
+  x_shape, labels_shape = tuple(int(v) for v in x_shape), tuple(int(v) for v in labels_shape)
+  if len(x_shape) != 2:
+    raise ValueError('%s: expected data of shape (m, d), got %s' % (what, x_shape))
+  if labels_shape not in ((x_shape[0],), (x_shape[0], 1)):
+    raise ValueError('%s: labels of shape %s for %d rows' % (what, labels_shape, x_shape[0]))
+  return x_shape[0], x_shape[1], label_size
 _extras = None
 
 
 def extras():
   """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve, fuzzy_step, lda_step,
-  affinity_degree / affinity_matrix);
+  affinity_degree / affinity_matrix, nb_step);
   raises if it has not been built."""
   global _extras
   if _extras is None:

@@ -1539,6 +1539,33 @@ class HipBackend(object):
     kernels.lda_step(x, n, alpha, eta, iters, delta=delta, doc_topics=doc_topics, splits=splits)
     return delta, doc_topics
 
+  def nb_step(self, x, labels, label_size, splits=0):
+    """The tile body of the reference's naive Bayes fit on a row tile as NEW tensors (S [label_size, d], df int64 [d],
+    bad int64 [1]): `x` [m, d] documents x terms, `labels` int64 [m] or [m, 1] (sp_nb_step: normalisation and label
+    sums fused, nothing of size m x d is allocated).  With r_i = sqrt(sum_j x_ij^2 / d):  S_lj = the sum over the rows
+    with labels_i == l of x_ij / r_i, in row order;  df_j = the rows with x_ij > 0;  bad = 0, or 1 + the lowest row
+    whose label is outside 0 .. label_size - 1 (it is left out of S and kept in df).  A row of zeros makes its label's
+    row of S NaN.  `x` fp32 or fp64; 1 <= label_size <= 128.  splits: into how many ranges the rows are cut (0: the
+    library chooses); df and bad do not depend on it.  The call counts as one launch when m > 0 and as none otherwise
+    (the three results are then zeros), and never waits for the device."""
+    x, labels = self._as_device(x), self._as_device(labels)
+    dt = self.dtype_of(x)
+    m, d, label_size = _hip.check_nb_operands(dt, x.shape, self.dtype_of(labels), labels.shape, label_size)
+    if int(splits) < 0:
+      raise ValueError('nb_step: splits = %d' % splits)
+    if not m:
+      return self.zeros((label_size, d), dt), self.zeros((d,), np.int64), self.zeros((1,), np.int64)
+    s, df, bad = self.empty((label_size, d), dt), self.empty((d,), np.int64), self.empty((1,), np.int64)
+    before = self.launches
+    if labels.dim() == 2:
+      labels = labels[:, 0]
+    if m > 1 and labels.stride(0) != 1:      # (a column of a wider array: the kernel reads the labels side by side)
+      labels = self.contiguous(labels)
+    x = self._knn_rows(x)
+    self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
+    kernels.nb_step(x, labels, label_size, s, df, bad, splits=splits)
+    return s, df, bad
+
   def affinity_degree(self, x, y, metric='rbf', gamma=1.0):
     """The degrees D_i = sum_j a(x_i, y_j) of the rows of `x` [m, d] against ALL rows of `y` [n, d] as a NEW tensor [m]
     (sp_affinity_degree: the affinities stay in registers, nothing of size m x n is allocated).  metric: 'rbf'

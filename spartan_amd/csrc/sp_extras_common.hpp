@@ -125,7 +125,17 @@ __global__ __launch_bounds__(256) void sp_partial_sum_kernel(const T* __restrict
     T a = (T)0;
     if (ranges > 0) {
       a = p[e];
-      for (int64_t g = 1; g < ranges; ++g) a = a + p[g * stride + e];
+      // eight loads at a time, then their additions in the same ascending order: with one load per trip the loop is
+      // a chain of memory latencies, which a caller with hundreds of ranges (sp_nb_step) waits for
+      int64_t g = 1;
+      for (; g + 8 <= ranges; g += 8) {
+        T v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = p[(g + i) * stride + e];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a = a + v[i];
+      }
+      for (; g < ranges; ++g) a = a + p[g * stride + e];
     }
     if (first) out[(e / cols) * ldo + e % cols] = a;
     else out2[e] = a;

@@ -11,5 +11,7 @@ embeds with sp_syevj; `als` (alternating least squares) solves every row's norma
 `lda.learn_topics` (LDA by collapsed variational Bayes) runs one sp_lda_step (the per-document loops fused) per tile of
 documents and pass; `spectral_clustering.spectral_cluster` finds the degrees with one sp_affinity_degree and writes the
 normalised affinity matrix with one sp_affinity_matrix per row band of the points (the affinity matrix itself is never
-stored), and `lanczos.solve` (float64 on the host around `dot`) hands its leading Ritz vectors to KMeans.
+stored), and `lanczos.solve` (float64 on the host around `dot`) hands its leading Ritz vectors to KMeans;
+`naive_bayes.fit` (the tf-idf naive Bayes classifier) runs one sp_nb_step (normalisation, label sums and document
+frequencies fused) per row band of the documents, `predict` / `predict_labels` score with `dot` and `argmax`.
 Like `sort` they are imported on first use, not with the package."""

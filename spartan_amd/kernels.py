@@ -678,6 +678,36 @@ def lda_step(x, n, alpha, eta, iters, delta=None, doc_topics=None, splits=0):
   return delta, doc_topics
 
 
+@_writes('out_s', 'out_df', 'out_bad')
+def nb_step(x, labels, label_size, out_s, out_df, out_bad, splits=0):
+  """The tile body of the reference's naive Bayes fit on a row tile (sp_nb_step; include/spartan_hip_nb.h states the
+  arithmetic and its order): `x` [m, d] fp32 or fp64, a view with inner stride 1; `labels` int64, [m] or an [m, 1]
+  view, its elements next to each other.  out_s [label_size, d] of x's dtype (a view with inner stride 1) <- the sum
+  over each label's rows of x_i / sqrt(mean_j x_ij^2), out_df [d] int64 contiguous <- the rows with x_ij > 0, out_bad
+  [1] int64 <- 0, or 1 + the lowest row whose label is outside 0 .. label_size - 1 (that row is left out of out_s
+  and kept in out_df).  splits: 0 = the library chooses into how many ranges the rows are cut, s >= 1 =
+  min(s, ceil(m / 64)) ranges.  TypeError for other dtypes, ValueError for label_size outside 1 .. 128 or shapes that
+  do not fit -- all before any launch.  Nothing waits for the device."""
+  _require_device(x, labels, out_s, out_df, out_bad)
+  dt = _float_dtype('nb_step', x, out_s)
+  m, d, label_size = _hip.check_nb_operands(dt, x.shape, np_dtype_of(labels), labels.shape, label_size)
+  if int(splits) < 0:
+    raise ValueError('nb_step: splits = %d' % splits)
+  if tuple(out_s.shape) != (label_size, d) or tuple(out_df.shape) != (d,) or tuple(out_bad.shape) != (1,):
+    raise ValueError('nb_step: targets of shapes %s, %s, %s for %d labels and %d features'
+                     % (tuple(out_s.shape), tuple(out_df.shape), tuple(out_bad.shape), label_size, d))
+  if np_dtype_of(out_df) != np.int64 or np_dtype_of(out_bad) != np.int64:
+    raise TypeError('nb_step: df and bad are int64, got %s and %s' % (np_dtype_of(out_df), np_dtype_of(out_bad)))
+  assert m <= 1 or labels.stride(0) == 1, labels.stride()
+  assert out_df.is_contiguous()
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  ws = _ws.get(lib.sp_nb_step_workspace_bytes(code, m, d, label_size, int(splits)), x.device)
+  check(lib.sp_nb_step(code, _p(x), _ld(x), m, d, _p(labels), label_size, int(splits), _p(out_s), _ld(out_s), _p(out_df),
+                       _p(out_bad), _p(ws), ws.numel(), _stream()))
+  return out_s, out_df, out_bad
+
+
 def affinity_operands(what, x, y, *others):
   """(dtype, m, n, d) of the operands of an affinity launcher, or its TypeError / ValueError."""
   dt = _float_dtype(what, x, y, *others)
