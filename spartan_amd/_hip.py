@@ -323,6 +323,11 @@ _EXTRAS_ABI = {
         'sp_nb_step': (C.c_int, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
         'sp_nb_step_workspace_bytes': (_sz, [_i32, _i64, _i64, _i64, _i32]),
     },
+    'spartan_hip_nbody.h': {
+        'sp_nbody_accel': (C.c_int, [_i32, _f64, _f64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _sz,
+                                     _vp]),
+        'sp_nbody_accel_workspace_bytes': (_sz, [_i32, _i64, _i64, _i32]),
+    },
 }
 EXPORTS_EXTRAS = list(_EXTRAS_ABI['spartan_hip_extras.h'])
 EXPORTS_EIG = list(_EXTRAS_ABI['spartan_hip_eig.h'])
@@ -333,6 +338,7 @@ EXPORTS_FUZZY = list(_EXTRAS_ABI['spartan_hip_fuzzy.h'])
 EXPORTS_LDA = list(_EXTRAS_ABI['spartan_hip_lda.h'])
 EXPORTS_SPECTRAL = list(_EXTRAS_ABI['spartan_hip_spectral.h'])
 EXPORTS_NB = list(_EXTRAS_ABI['spartan_hip_nb.h'])
+EXPORTS_NBODY = list(_EXTRAS_ABI['spartan_hip_nbody.h'])
 KNN_MAX_K = 128       # SP_KNN_MAX_K of spartan_hip_knn.h
 SP_ALS_MAX_F = 64     # of spartan_hip_als.h
 SP_LDA_MAX_K = 128    # of spartan_hip_lda.h
@@ -374,12 +380,46 @@ def check_nb_operands(x_dtype, x_shape, labels_dtype, labels_shape, label_size, 
   if labels_shape not in ((x_shape[0],), (x_shape[0], 1)):
     raise ValueError('%s: labels of shape %s for %d rows' % (what, labels_shape, x_shape[0]))
   return x_shape[0], x_shape[1], label_size
+
+
+def check_nbody_operands(dtypes, shapes, r0, m, g, rmin, splits=0, what='nbody_accel'):
+  """(dtype, n, r0, m, g, rmin, splits) of an all-pairs gravity call on x, y, z and mass -- `dtypes` and `shapes` are
+  theirs, in that order -- or what sp_nbody_accel refuses: TypeError ("astype first") for arrays that are not float32 /
+  float64 or that are of two dtypes; ValueError for arrays that are not 1-D and of equal length, targets r0 .. r0 + m
+  that are not among the n bodies, splits < 0, a g that is not finite in the arrays' dtype and an rmin that is not
+  finite and > 0 in it.  The one copy: the launcher, the backend, the NumPy body of examples/_nbody.py and the driver
+  all refuse through it."""
+  dtypes = [np.dtype(d) for d in dtypes]
+  for d in dtypes:
+    if d not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, d))
+  for d in dtypes[1:]:
+    if d != dtypes[0]:
+      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, dtypes[0], d))
+  shapes = [tuple(int(v) for v in s) for s in shapes]
+  if any(len(s) != 1 for s in shapes) or any(s != shapes[0] for s in shapes):
+    raise ValueError('%s: x, y, z and mass must be 1-D and of equal length, got shapes %s' % (what, shapes))
+  n, r0, m, splits = shapes[0][0], int(r0), int(m), int(splits)
+  if r0 < 0 or m < 0 or r0 + m > n:
+    raise ValueError('%s: bodies %d .. %d are not among the %d' % (what, r0, r0 + m, n))
+  if splits < 0:
+    raise ValueError('%s: splits = %d' % (what, splits))
+  g, rmin = float(g), float(rmin)
+  with np.errstate(all='ignore'):
+    gt, rt = dtypes[0].type(g), dtypes[0].type(rmin)
+  if not np.isfinite(gt):
+    raise ValueError('%s: g = %r must be finite in %s' % (what, g, dtypes[0]))
+  if not (rt > 0 and np.isfinite(rt)):
+    raise ValueError('%s: rmin = %r must be finite and > 0 in %s' % (what, rmin, dtypes[0]))
+  return dtypes[0], n, r0, m, g, rmin, splits
+
+
 _extras = None
 
 
 def extras():
   """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve, fuzzy_step, lda_step,
-  affinity_degree / affinity_matrix, nb_step);
+  affinity_degree / affinity_matrix, nb_step, nbody_accel);
   raises if it has not been built."""
   global _extras
   if _extras is None:

@@ -1566,6 +1566,28 @@ class HipBackend(object):
     kernels.nb_step(x, labels, label_size, s, df, bad, splits=splits)
     return s, df, bad
 
+  def nbody_accel(self, x, y, z, mass, r0, m, g=6.67384e-11, rmin=1.0, splits=0):
+    """(ax, ay, az) as NEW tensors [m], the rows of one [3, m] array: the accelerations of bodies r0 .. r0 + m - 1 of
+    `x`, `y`, `z`, `mass` [n] under the gravity of all n (sp_nbody_accel: every pair in registers, nothing of size
+    n x n is allocated):  a_x[j] = sum over i != j of (g mass_i) / max(r_ij, rmin)^3 * (x_i - x_j), y and z alike.  All
+    four fp32 or all fp64.  The bits of a[j] depend on body j, the n sources and (n, splits) alone, so a band of targets
+    computed alone gives the bits the whole gives.  splits: into how many ranges the sources are cut (0: the library
+    chooses from n).  A strided view is first made contiguous.  The library issues one kernel with one range and two
+    with more (the second adds the ranges' partial sums), and the call counts as that many launches -- none when
+    m = 0 -- and never waits for the device.  Refusals: _hip.check_nbody_operands'."""
+    operands = [self._as_device(t) for t in (x, y, z, mass)]
+    dt, n, r0, m, g, rmin, splits = _hip.check_nbody_operands([self.dtype_of(t) for t in operands],
+                                                             [t.shape for t in operands], r0, m, g, rmin, splits)
+    before = self.launches
+    out = self.empty((3, m), dt)
+    if m:
+      operands = [self.contiguous(t) for t in operands]
+      kernels.nbody_accel(*operands, r0, m, out[0], out[1], out[2], g, rmin, splits=splits)
+      blocks = -(-n // 64)       # (the library's choice of ranges, nbody_ranges of csrc/nbody.hip, to count its launches)
+      ranges = 1 if blocks <= 1 else min(splits, blocks) if splits else min(-(-1024 // blocks), blocks)
+      self.launches = before + (1 if ranges == 1 else 2)   # (a strided operand's copy belongs to the call)
+    return out[0], out[1], out[2]
+
   def affinity_degree(self, x, y, metric='rbf', gamma=1.0):
     """The degrees D_i = sum_j a(x_i, y_j) of the rows of `x` [m, d] against ALL rows of `y` [n, d] as a NEW tensor [m]
     (sp_affinity_degree: the affinities stay in registers, nothing of size m x n is allocated).  metric: 'rbf'

@@ -13,5 +13,7 @@ documents and pass; `spectral_clustering.spectral_cluster` finds the degrees wit
 normalised affinity matrix with one sp_affinity_matrix per row band of the points (the affinity matrix itself is never
 stored), and `lanczos.solve` (float64 on the host around `dot`) hands its leading Ritz vectors to KMeans;
 `naive_bayes.fit` (the tf-idf naive Bayes classifier) runs one sp_nb_step (normalisation, label sums and document
-frequencies fused) per row band of the documents, `predict` / `predict_labels` score with `dot` and `argmax`.
+frequencies fused) per row band of the documents, `predict` / `predict_labels` score with `dot` and `argmax`;
+`nbody.move` / `simulate` (all-pairs gravity) runs one sp_nbody_accel (every pair in registers, nothing of size n x n)
+per band of bodies and updates velocities and positions on the map kernels.
 Like `sort` they are imported on first use, not with the package."""

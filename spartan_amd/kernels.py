@@ -708,6 +708,32 @@ def nb_step(x, labels, label_size, out_s, out_df, out_bad, splits=0):
   return out_s, out_df, out_bad
 
 
+@_writes('ax', 'ay', 'az')
+def nbody_accel(x, y, z, mass, r0, m, ax, ay, az, g, rmin, splits=0):
+  """The accelerations of bodies r0 .. r0 + m - 1 under the gravity of all n (sp_nbody_accel;
+  include/spartan_hip_nbody.h states the arithmetic of a pair and the order of a target's sum): `x`, `y`, `z`, `mass`
+  contiguous [n], all fp32 or all fp64; ax, ay, az contiguous [m] of their dtype <- sum over i != j of
+  (g mass_i) / max(r_ij, rmin)^3 * (x_i - x_j) (y, z alike).  Nothing of size n x n is stored.  splits: 0 = the
+  library chooses from n into how many ranges the sources are cut, s >= 1 = min(s, ceil(n / 64)) ranges.  TypeError for
+  other or mixed dtypes, ValueError for shapes that do not fit, targets that are not among the bodies, splits < 0, a g
+  that is not finite or an rmin that is not finite and > 0 -- all before any launch.  Owns the workspace.  Nothing
+  waits for the device."""
+  _require_device(x, y, z, mass, ax, ay, az)
+  operands = (x, y, z, mass, ax, ay, az)
+  dt, n, r0, m, g, rmin, splits = _hip.check_nbody_operands([np_dtype_of(t) for t in operands],
+                                                           [t.shape for t in operands[:4]], r0, m, g, rmin, splits)
+  if any(tuple(t.shape) != (m,) for t in (ax, ay, az)):
+    raise ValueError('nbody_accel: targets of shapes %s for %d bodies' % ([tuple(t.shape) for t in (ax, ay, az)], m))
+  assert all(t.is_contiguous() for t in operands), [t.stride() for t in operands]
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  need = lib.sp_nbody_accel_workspace_bytes(code, n, m, splits)
+  ws = _ws.get(need, x.device) if need else None
+  check(lib.sp_nbody_accel(code, g, rmin, _p(x), _p(y), _p(z), _p(mass), n, r0, m, _p(ax), _p(ay), _p(az), splits, _p(ws),
+                           ws.numel() if need else 0, _stream()))
+  return ax, ay, az
+
+
 def affinity_operands(what, x, y, *others):
   """(dtype, m, n, d) of the operands of an affinity launcher, or its TypeError / ValueError."""
   dt = _float_dtype(what, x, y, *others)
