@@ -328,6 +328,12 @@ _EXTRAS_ABI = {
                                      _vp]),
         'sp_nbody_accel_workspace_bytes': (_sz, [_i32, _i64, _i64, _i32]),
     },
+    'spartan_hip_cf.h': {
+        'sp_item_topk_workspace_bytes': (_sz, [_i32, _i64, _i64, _i64, _i32, _i32]),
+        'sp_item_topk': (C.c_int, [_i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _vp,
+                                   _sz, _vp]),
+        'sp_item_topk_merge': (C.c_int, [_i32, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    },
 }
 EXPORTS_EXTRAS = list(_EXTRAS_ABI['spartan_hip_extras.h'])
 EXPORTS_EIG = list(_EXTRAS_ABI['spartan_hip_eig.h'])
@@ -339,7 +345,9 @@ EXPORTS_LDA = list(_EXTRAS_ABI['spartan_hip_lda.h'])
 EXPORTS_SPECTRAL = list(_EXTRAS_ABI['spartan_hip_spectral.h'])
 EXPORTS_NB = list(_EXTRAS_ABI['spartan_hip_nb.h'])
 EXPORTS_NBODY = list(_EXTRAS_ABI['spartan_hip_nbody.h'])
+EXPORTS_CF = list(_EXTRAS_ABI['spartan_hip_cf.h'])
 KNN_MAX_K = 128       # SP_KNN_MAX_K of spartan_hip_knn.h
+CF_MAX_K = 128        # SP_CF_MAX_K of spartan_hip_cf.h (tests/test_cf_cases_cpu.py keeps the two equal)
 SP_ALS_MAX_F = 64     # of spartan_hip_als.h
 SP_LDA_MAX_K = 128    # of spartan_hip_lda.h
 SP_NB_MAX_LABELS = 128   # of spartan_hip_nb.h
@@ -414,12 +422,42 @@ def check_nbody_operands(dtypes, shapes, r0, m, g, rmin, splits=0, what='nbody_a
   return dtypes[0], n, r0, m, g, rmin, splits
 
 
+def check_item_topk_operands(dtypes, t_shape, tnorm_shape, s_shape, snorm_shape, k, splits=0, what='item_topk'):
+  """(dtype, users, m, ns, k, splits) of a cosine top-k call on targets [users, m], tnorm [m], sources [users, ns] and
+  snorm [ns] -- `dtypes` are theirs, in that order -- or what sp_item_topk refuses: TypeError ("astype first") for
+  operands that are not float32 / float64 or that are of two dtypes; ValueError for targets or sources that are not 2-D,
+  user counts that differ, norms that are not [m] and [ns], a k outside 1 .. CF_MAX_K and splits < 0.  The one copy:
+  the launcher, the backend, the NumPy body of examples/cf/_cf.py and the driver all refuse through it."""
+  dtypes = [np.dtype(d) for d in dtypes]
+  for d in dtypes:
+    if d not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, d))
+  for d in dtypes[1:]:
+    if d != dtypes[0]:
+      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, dtypes[0], d))
+  t_shape, s_shape = tuple(int(v) for v in t_shape), tuple(int(v) for v in s_shape)
+  tnorm_shape, snorm_shape = tuple(int(v) for v in tnorm_shape), tuple(int(v) for v in snorm_shape)
+  if len(t_shape) != 2 or len(s_shape) != 2:
+    raise ValueError('%s: targets and sources must be 2-D [users, items], got shapes %s and %s' % (what, t_shape, s_shape))
+  if t_shape[0] != s_shape[0]:
+    raise ValueError('%s: targets of %d users against sources of %d' % (what, t_shape[0], s_shape[0]))
+  if tnorm_shape != (t_shape[1],) or snorm_shape != (s_shape[1],):
+    raise ValueError('%s: norms of shapes %s and %s for %d targets and %d sources'
+                     % (what, tnorm_shape, snorm_shape, t_shape[1], s_shape[1]))
+  k, splits = int(k), int(splits)
+  if not 1 <= k <= CF_MAX_K:
+    raise ValueError('%s: k = %d is outside 1 .. %d' % (what, k, CF_MAX_K))
+  if splits < 0:
+    raise ValueError('%s: splits = %d is negative' % (what, splits))
+  return dtypes[0], t_shape[0], t_shape[1], s_shape[1], k, splits
+
+
 _extras = None
 
 
 def extras():
   """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve, fuzzy_step, lda_step,
-  affinity_degree / affinity_matrix, nb_step, nbody_accel);
+  affinity_degree / affinity_matrix, nb_step, nbody_accel, item_topk);
   raises if it has not been built."""
   global _extras
   if _extras is None:

@@ -1402,6 +1402,64 @@ class HipBackend(object):
       kernels.knn_merge(cand_dist2, cand_idx, k, dist2, idx)
     return dist2, idx
 
+  def item_topk(self, targets, tnorm, sources, snorm, k, index_offset=0, splits=0):
+    """(sim, idx) as NEW tensors [m, k]: for every column j of `targets` [users, m] the k columns i of `sources`
+    [users, ns] of the largest cosine similarity nan_to_num(dot_u(t[u][j], s[u][i]) / (tnorm[j] * snorm[i])), ordered
+    by (similarity descending, index ascending); idx (int64) = index_offset + column of `sources`; -inf / -1 in the
+    trailing slots when ns < k (sp_item_topk: similarity and selection in one pass, nothing of size m x ns is written;
+    include/spartan_hip_cf.h states the order of the arithmetic).  All four operands fp32 or all fp64; 1 <= k <= 128.
+    A target is not excluded from its own list.  splits: into how many ranges the sources are cut (0: the library
+    chooses); the result does not depend on it, nor on how the targets are banded, bit for bit.  Operands whose inner
+    stride is not 1 are first copied contiguous; two column ranges of one table are taken as they are.  The library
+    issues one kernel with one range and two with more (the second merges the ranges' candidates), and the call counts
+    as that many launches -- none when m = 0.  Refusals: _hip.check_item_topk_operands'."""
+    targets, tnorm, sources, snorm = (self._as_device(t) for t in (targets, tnorm, sources, snorm))
+    dt, users, m, ns, k, splits = _hip.check_item_topk_operands(
+        [self.dtype_of(t) for t in (targets, tnorm, sources, snorm)], targets.shape, tnorm.shape, sources.shape,
+        snorm.shape, k, splits)
+    before = self.launches
+    sim, idx = self.empty((m, k), dt), self.empty((m, k), np.int64)
+    if m:
+      kernels.item_topk(self._knn_rows(targets), self.contiguous(tnorm), self._knn_rows(sources), self.contiguous(snorm),
+                        k, sim, idx, index_offset, splits)
+      # (the library's choice of ranges, cf_ranges of csrc/cf.hip, to count its launches)
+      if ns <= 0:
+        ranges = 1
+      elif splits:
+        ranges = min(splits, ns)
+      else:
+        ranges = max(1, min(-(-512 // -(-m // 64)), -(-ns // max(4 * k, 64)), 64))
+        if ranges > 1:
+          ranges = -(-ns // (64 * -(-(-(-ns // ranges)) // 64)))
+      self.launches = before + (1 if ranges == 1 else 2)   # (a strided operand's copy belongs to the call)
+    return sim, idx
+
+  def item_topk_merge(self, cand_sim, cand_idx, k):
+    """(sim, idx) as NEW tensors [m, k]: per row the k best by (similarity descending, index ascending) of the
+    candidates (cand_sim fp32 / fp64, cand_idx int64, both [m, cands]); candidates with a negative index are padding,
+    and so are the trailing slots of the result (-inf / -1) when fewer than k are left (sp_item_topk_merge)."""
+    cand_sim, cand_idx = self._as_device(cand_sim), self._as_device(cand_idx)
+    dt = self.dtype_of(cand_sim)
+    _hip.refuse_not_float(dt, 'item_topk_merge')
+    if self.dtype_of(cand_idx) != np.int64:
+      raise TypeError('item_topk_merge: candidate indices of dtype %s (int64 expected); convert with astype first'
+                      % (self.dtype_of(cand_idx),))
+    if cand_sim.dim() != 2 or tuple(cand_sim.shape) != tuple(cand_idx.shape):
+      raise ValueError('item_topk_merge: shapes %s and %s do not fit' % (tuple(cand_sim.shape), tuple(cand_idx.shape)))
+    k = int(k)
+    if not 1 <= k <= _hip.CF_MAX_K:
+      raise ValueError('item_topk_merge: k = %d is outside 1 .. %d' % (k, _hip.CF_MAX_K))
+    m = int(cand_sim.shape[0])
+    sim, idx = self.empty((m, k), dt), self.empty((m, k), np.int64)
+    if m:
+      before = self.launches
+      cand_sim, cand_idx = self._knn_rows(cand_sim), self._knn_rows(cand_idx)
+      if m > 1 and cand_sim.stride(0) != cand_idx.stride(0):      # (the kernel takes one row stride for both)
+        cand_sim, cand_idx = self.contiguous(cand_sim), self.contiguous(cand_idx)
+      kernels.item_topk_merge(cand_sim, cand_idx, k, sim, idx)
+      self.launches = before + 1
+    return sim, idx
+
   def apsp(self, t):
     """The matrix of shortest-path lengths as a NEW tensor: `t` [n, n], fp32 / fp64, holds the edge lengths of a
     directed graph (>= 0, +inf = no edge, the diagonal taken as 0; a symmetric `t` is an undirected graph); the result

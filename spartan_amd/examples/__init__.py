@@ -15,5 +15,7 @@ stored), and `lanczos.solve` (float64 on the host around `dot`) hands its leadin
 `naive_bayes.fit` (the tf-idf naive Bayes classifier) runs one sp_nb_step (normalisation, label sums and document
 frequencies fused) per row band of the documents, `predict` / `predict_labels` score with `dot` and `argmax`;
 `nbody.move` / `simulate` (all-pairs gravity) runs one sp_nbody_accel (every pair in registers, nothing of size n x n)
-per band of bodies and updates velocities and positions on the map kernels.
+per band of bodies and updates velocities and positions on the map kernels;
+`cf.ItemBasedRecommender` (item-based collaborative filtering) runs one sp_item_topk (cosine similarity and top-k fused,
+nothing of size N x N) per column band and source step of the rating table and merges the steps with sp_item_topk_merge.
 Like `sort` they are imported on first use, not with the package."""

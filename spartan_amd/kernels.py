@@ -535,6 +535,48 @@ def knn_merge(cand_dist2, cand_idx, k, dist2, idx):
   return dist2, idx
 
 
+@_writes('sim', 'idx')
+def item_topk(targets, tnorm, sources, snorm, k, sim, idx, index_offset=0, splits=0):
+  """sim[j], idx[j] <- the k columns of `sources` [users, ns] of the largest cosine similarity with column j of
+  `targets` [users, m], by (similarity descending, index ascending); idx = index_offset + column of sources, padded
+  with -inf / -1 when ns < k (sp_item_topk; include/spartan_hip_cf.h states the arithmetic: dot over the users in
+  ascending order, / (tnorm[j] * snorm[i]), nan_to_num).  targets, sources: both fp32 or both fp64, views with inner
+  stride 1 (two column ranges of one table will do); tnorm [m], snorm [ns] contiguous, of their dtype; sim (their
+  dtype) and idx (int64): contiguous [m, k].  splits: 0 = the library chooses into how many ranges the sources are cut,
+  s >= 1 = min(s, ns) ranges.  Refusals: _hip.check_item_topk_operands', before any launch.  Owns the workspace."""
+  _require_device(targets, tnorm, sources, snorm, sim, idx)
+  dt, users, m, ns, k, splits = _hip.check_item_topk_operands(
+      [np_dtype_of(t) for t in (targets, tnorm, sources, snorm, sim)], targets.shape, tnorm.shape, sources.shape,
+      snorm.shape, k, splits)
+  assert np_dtype_of(idx) == np.int64 and tnorm.is_contiguous() and snorm.is_contiguous()
+  assert tuple(sim.shape) == (m, k) and tuple(idx.shape) == (m, k) and sim.is_contiguous() and idx.is_contiguous()
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  need = lib.sp_item_topk_workspace_bytes(code, users, m, ns, k, splits)
+  ws = _ws.get(need, targets.device) if need else None
+  check(lib.sp_item_topk(code, _p(targets), _ld(targets), _p(tnorm), m, _p(sources), _ld(sources), _p(snorm), ns, users,
+                         k, int(index_offset), splits, _p(sim), _p(idx), _p(ws), ws.numel() if need else 0, _stream()))
+  return sim, idx
+
+
+@_writes('sim', 'idx')
+def item_topk_merge(cand_sim, cand_idx, k, sim, idx):
+  """sim[j], idx[j] <- the k best by (similarity descending, index ascending) of the candidates of row j; candidates
+  with a negative index are padding (sp_item_topk_merge).  cand_sim (fp32 / fp64) and cand_idx (int64): [m, cands]
+  views with inner stride 1 and ONE row stride; sim, idx: contiguous [m, k]."""
+  _require_device(cand_sim, cand_idx, sim, idx)
+  dt = _float_dtype('item_topk_merge', cand_sim)
+  assert np_dtype_of(cand_idx) == np.int64 and np_dtype_of(idx) == np.int64 and np_dtype_of(sim) == dt
+  assert cand_sim.dim() == 2 and tuple(cand_sim.shape) == tuple(cand_idx.shape)
+  m, cands = (int(v) for v in cand_sim.shape)
+  k = int(k)
+  assert _ld(cand_sim) == _ld(cand_idx), (cand_sim.stride(), cand_idx.stride())
+  assert tuple(sim.shape) == (m, k) and tuple(idx.shape) == (m, k) and sim.is_contiguous() and idx.is_contiguous()
+  check(_hip.extras().sp_item_topk_merge(_hip.sp_dtype(dt), _p(cand_sim), _p(cand_idx), _ld(cand_sim), m, cands, k,
+                                         _p(sim), _p(idx), _stream()))
+  return sim, idx
+
+
 @_writes('d', 'info')
 def apsp(d, info):
   """In place: the square fp32 / fp64 matrix `d` of edge lengths (>= 0, +inf = no edge, the diagonal taken as 0; a view
