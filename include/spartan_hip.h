@@ -283,16 +283,37 @@ int sp_argreduce(const sp_program* prog, const void* const* d_inputs, int32_t wh
 int sp_update(void* d_dst, int32_t dst_dtype, const int64_t* dst_shape, int32_t ndim,
               const int64_t* ul, const int64_t* lr, const void* d_src, int32_t src_dtype,
               int32_t reducer, int32_t mask_mode, uint8_t* d_mask, void* stream);
+/* Which kernel sp_update would launch for these arguments (host code: nothing is launched, no pointer is
+ * dereferenced; the launch itself asks the same function).  *compute_class: SP_F16 (float arithmetic, the reduced
+ * value rounded to half), SP_F32, SP_F64 or SP_I64.  *vector_width: elements per thread step -- 4 (float classes)
+ * or 2 (double, int64) when the box's innermost extent, the box origin's offset, every outer stride of the tile and
+ * both pointers (16 bytes) allow it, else 1; 0 for an empty box (nothing is launched).  Refuses what the launch
+ * refuses (rank, NULL pointers, dtypes, a box outside the tile). */
+int sp_update_path(const void* d_dst, int32_t dst_dtype, const int64_t* dst_shape, int32_t ndim,
+                   const int64_t* ul, const int64_t* lr, const void* d_src, int32_t src_dtype,
+                   int32_t* compute_class, int32_t* vector_width);
 
 /* sp_slice_copy: strided <=4-d box copy (element size 1/2/4/8 bytes) used by
  * DistArrayImpl.fetch's stitch `tgt[dst_slice] = result`
  * (spartan/array/distarray.py:355-365), Tile.get(subslice) (tile.pyx:64-113)
  * and sparse.multiple_slice's dense branch (sparse.pyx:297-301).
- * Strides are in ELEMENTS.
+ * Strides are in ELEMENTS and may be negative or (source only) zero.
+ * The bytes read and the bytes written must be DISJOINT: the kernels read and
+ * write in no defined order.  A caller whose source and destination may
+ * overlap copies the source first (HipBackend.paste does).
  */
 int sp_slice_copy(void* d_dst, const int64_t* dst_stride, const void* d_src,
                   const int64_t* src_stride, const int64_t* shape, int32_t ndim,
                   int32_t elem_size, void* stream);
+/* Which kernel sp_slice_copy would launch for these arguments (host code: nothing is launched, no pointer is
+ * dereferenced; the launch itself asks the same function).  *word_bytes: the bytes one thread step moves -- the
+ * element size, or 16 when the box is widened (innermost stride 1 on both sides, innermost extent and every outer
+ * stride a multiple of 16 / elem_size elements, both pointers 16-byte aligned); 0 for an empty box (nothing is
+ * launched).  *transpose: 1 when the LDS-tiled transpose kernel is taken (2-d, 2/4/8-byte elements, both extents at
+ * least 16, dst rows dense, src walking a column).  Refuses what the launch refuses. */
+int sp_slice_copy_path(const void* d_dst, const int64_t* dst_stride, const void* d_src,
+                       const int64_t* src_stride, const int64_t* shape, int32_t ndim,
+                       int32_t elem_size, int32_t* word_bytes, int32_t* transpose);
 
 /* sp_gemm_f32: C[M,N] (+)= A[M,K] . B[K,N], fp32 in / fp32 accumulate on the
  * f32 MFMA (v_mfma_f32_32x32x2_f32).  Row-major with leading dimensions in
@@ -589,7 +610,8 @@ int sp_memset(void* d_dst, int32_t value, size_t bytes, void* stream);
  *                               array: the box [ul, lr) of the blob (NULL, NULL = all of it) <-> a contiguous
  *                               host buffer of the box's shape; asynchronous on `stream`.
  *   sp_blob_slice_copy          `get` + `update(reducer=None)` between two tiles of one worker: the fetch stitch
- *                               of spartan/array/distarray.py:355-365 on handles. */
+ *                               of spartan/array/distarray.py:355-365 on handles.  Two boxes of ONE blob must be
+ *                               disjoint (sp_slice_copy's precondition). */
 int sp_blob_create(const int64_t* shape, int32_t ndim, int32_t dtype, uint64_t* handle);
 int sp_blob_destroy(uint64_t handle);
 int sp_blob_trim(void);

@@ -547,12 +547,15 @@ class HipBackend(object):
 
   # -- strided views ----------------------------------------------------------------
   def paste(self, dst, dst_slices, src):
-    """dst[dst_slices] = src (strided box copy in HBM)."""
+    """dst[dst_slices] = src (strided box copy in HBM).  A source that may overlap the destination (`d[1:] = d[:-1]`)
+    is copied first, as NumPy does: sp_slice_copy needs disjoint ranges."""
     view = dst[dst_slices] if dst.dim() else dst
     if tuple(view.shape) != tuple(src.shape):
       src = src.reshape(view.shape)
     if view.numel() == 0:
       return
+    if D.may_overlap(view, src):
+      src = self.copy(src)
     self._wrote(dst)
     if self.dtype_of(view) != self.dtype_of(src):
       raise _hip.HipError('paste: dtype mismatch %s vs %s' % (self.dtype_of(view), self.dtype_of(src)))

@@ -94,10 +94,11 @@ bool box_is_whole(const Blob& b, const int64_t* ext) {
 }
 
 // One contiguous byte range?  (every axis before the first cut one has extent 1, every axis after it is whole:
-// a run of rows of a matrix, any range of a 1-D blob.)
+// a run of rows of a matrix, any range of a 1-D blob.  A leading axis of length 1 is a single index like any other:
+// rows 1..3 of a 1 x 5 x 6 blob are one range.)
 bool box_is_contiguous(const Blob& b, const int64_t* ext) {
   int i = 0;
-  while (i < b.ndim && ext[i] == 1 && b.shape[i] != 1) ++i;     // leading single indices
+  while (i < b.ndim && ext[i] == 1) ++i;                         // leading single indices
   if (i < b.ndim) ++i;                                           // the one axis that may be a proper range
   for (; i < b.ndim; ++i)
     if (ext[i] != b.shape[i]) return false;

@@ -221,13 +221,18 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_transpose_kernel(E* __restrict__ 
   }
 }
 
-extern "C" int sp_slice_copy(void* d_dst, const int64_t* dst_stride, const void* d_src,
-                             const int64_t* src_stride, const int64_t* shape, int32_t ndim,
-                             int32_t elem_size, void* stream) {
+// What one sp_slice_copy call launches: the ONE place that decides it, used by the launch and by the query
+// sp_slice_copy_path.  `word` = bytes one thread step moves (the element size, or 16 when the box is widened; 0 for an
+// empty box: nothing is launched), `transpose` = the LDS-tiled kernel.  On return `b` / `n` are what the chosen kernel
+// takes: the box folded into 16-byte words when it is widened.  Host code only: no pointer is dereferenced.
+static int sp_slice_copy_choose(const void* d_dst, const int64_t* dst_stride, const void* d_src,
+                                const int64_t* src_stride, const int64_t* shape, int32_t ndim, int32_t elem_size,
+                                BoxDesc* box, int64_t* count, int32_t* word, int32_t* transpose) {
   if (ndim < 0 || ndim > SP_MAX_DIMS) SP_FAIL("sp_slice_copy: ndim=%d unsupported (max %d)", ndim, SP_MAX_DIMS);
   if (elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8) SP_FAIL("sp_slice_copy: elem_size=%d", elem_size);
   if (!d_dst || !d_src) SP_FAIL("sp_slice_copy: NULL pointer");
-  BoxDesc b;
+  if (ndim > 0 && (!dst_stride || !src_stride || !shape)) SP_FAIL("sp_slice_copy: NULL shape / strides");
+  BoxDesc& b = *box;
   memset(&b, 0, sizeof(b));
   int64_t n = 1;
   if (ndim == 0) {
@@ -244,11 +249,59 @@ extern "C" int sp_slice_copy(void* d_dst, const int64_t* dst_stride, const void*
       n *= shape[d];
     }
   }
+  *count = n;
+  *word = 0;
+  *transpose = 0;
   if (n == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
+  *word = elem_size;
   // 2-D transpose pattern (dst dense rows, src walks a column): LDS-tiled kernel
   if (b.ndim == 2 && (elem_size == 2 || elem_size == 4 || elem_size == 8) && b.dstride[1] == 1 && b.sstride[0] == 1 &&
       b.sstride[1] >= b.shape[0] && b.dstride[0] >= b.shape[1] && b.shape[0] >= 16 && b.shape[1] >= 16) {
+    *transpose = 1;
+    return 0;
+  }
+  // widen: if the innermost run is contiguous on both sides, move 16-B words
+  const int last = b.ndim - 1;
+  if (b.dstride[last] == 1 && b.sstride[last] == 1) {
+    const int64_t per16 = 16 / elem_size;
+    bool ok = (b.shape[last] % per16 == 0) && ((((uintptr_t)d_dst) | ((uintptr_t)d_src)) & 15) == 0;
+    for (int d = 0; d < last && ok; ++d)
+      if (b.dstride[d] % per16 != 0 || b.sstride[d] % per16 != 0) ok = false;
+    if (ok) {
+      b.shape[last] /= per16;
+      for (int d = 0; d < last; ++d) {
+        b.dstride[d] /= per16;
+        b.sstride[d] /= per16;
+      }
+      *count = n / per16;
+      *word = 16;
+    }
+  }
+  return 0;
+}
+
+extern "C" int sp_slice_copy_path(const void* d_dst, const int64_t* dst_stride, const void* d_src,
+                                  const int64_t* src_stride, const int64_t* shape, int32_t ndim, int32_t elem_size,
+                                  int32_t* word_bytes, int32_t* transpose) {
+  BoxDesc b;
+  int64_t n;
+  int32_t word = 0, tr = 0;
+  if (sp_slice_copy_choose(d_dst, dst_stride, d_src, src_stride, shape, ndim, elem_size, &b, &n, &word, &tr)) return 1;
+  if (word_bytes) *word_bytes = word;
+  if (transpose) *transpose = tr;
+  return 0;
+}
+
+extern "C" int sp_slice_copy(void* d_dst, const int64_t* dst_stride, const void* d_src,
+                             const int64_t* src_stride, const int64_t* shape, int32_t ndim,
+                             int32_t elem_size, void* stream) {
+  BoxDesc b;
+  int64_t n;
+  int32_t word = 0, transpose = 0;
+  if (sp_slice_copy_choose(d_dst, dst_stride, d_src, src_stride, shape, ndim, elem_size, &b, &n, &word, &transpose)) return 1;
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (transpose) {
     // dst[i][j] = src[j][i] with src row-major of leading dimension sstride[1]
     const int64_t R = b.shape[1], Cc = b.shape[0];   // src is R x Cc
     int64_t blocks = ((R + 63) / 64) * ((Cc + 63) / 64);
@@ -266,26 +319,8 @@ extern "C" int sp_slice_copy(void* d_dst, const int64_t* dst_stride, const void*
     SP_CHECK_LAUNCH();
     return 0;
   }
-  // widen: if the innermost run is contiguous on both sides, move 16-B words
-  const int last = b.ndim - 1;
-  int64_t es = elem_size;
-  if (b.dstride[last] == 1 && b.sstride[last] == 1) {
-    const int64_t per16 = 16 / es;
-    bool ok = (b.shape[last] % per16 == 0) && ((((uintptr_t)d_dst) | ((uintptr_t)d_src)) & 15) == 0;
-    for (int d = 0; d < last && ok; ++d)
-      if (b.dstride[d] % per16 != 0 || b.sstride[d] % per16 != 0) ok = false;
-    if (ok) {
-      b.shape[last] /= per16;
-      for (int d = 0; d < last; ++d) {
-        b.dstride[d] /= per16;
-        b.sstride[d] /= per16;
-      }
-      n /= per16;
-      es = 16;
-    }
-  }
   const dim3 g(grid_for(n)), blk(SP_BLOCK);
-  switch (es) {
+  switch (word) {
     case 16:
       hipLaunchKernelGGL((sp_box_copy_kernel<float4>), g, blk, 0, st, (float4*)d_dst, (const float4*)d_src, b, n);
       break;
@@ -316,11 +351,27 @@ struct UpdDesc {
   int32_t round_f16;             // NumPy reduces in float16: the reduced value is rounded to half before the astype
 };
 
+// NaN + NaN, NaN * NaN: IEEE 754 leaves open WHICH operand's payload the result carries.  The hardware takes it by
+// operand position and the compiler may swap the operands of a commutative instruction: the vector and the scalar
+// instantiation of the kernel below came out differently, so the bytes of a merge depended on the box's alignment.
+// NumPy's own loops differ among themselves as well; its contiguous (SIMD) add and multiply loops on x86-64 return the
+// SECOND operand -- the update --, quieted.  So does this, in every instantiation.
+template <typename T>
+__device__ __forceinline__ T sp_nan_of_update(T old, T upd, T res) {
+  if constexpr (sp_is_same<T, float>::value) {
+    if (old != old && upd != upd) return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, upd) | 0x00400000u);
+  } else if constexpr (sp_is_same<T, double>::value) {
+    if (old != old && upd != upd)
+      return __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, upd) | 0x0008000000000000ull);
+  }
+  return res;
+}
+
 template <typename T>
 __device__ __forceinline__ T sp_apply_reducer(int r, T old, T upd) {
   switch (r) {
-    case SP_REDUCER_ADD: return old + upd;
-    case SP_REDUCER_MUL: return old * upd;
+    case SP_REDUCER_ADD: return sp_nan_of_update<T>(old, upd, old + upd);
+    case SP_REDUCER_MUL: return sp_nan_of_update<T>(old, upd, old * upd);
     case SP_REDUCER_MAX: return sp_nanmax<T>(old, upd);
     case SP_REDUCER_MIN: return sp_nanmin<T>(old, upd);
     case SP_REDUCER_AND: return (T)((old != (T)0) && (upd != (T)0));
@@ -425,42 +476,23 @@ static int sp_merge_class(int32_t dst, int32_t src) {
   return level == 0 ? SP_F16 : (level == 1 ? SP_F32 : SP_F64);
 }
 
-template <typename T>
-static int sp_update_launch(void* d_dst, const void* d_src, uint8_t* d_mask, const UpdDesc& u, int64_t n,
-                            hipStream_t st) {
-  constexpr int VV = sp_cls<T>::V;
-  const int last = u.ndim - 1;
-  bool vec = (u.box[last] % VV == 0) && (u.doff % VV == 0) &&
-             ((((uintptr_t)d_dst) | ((uintptr_t)d_src)) & 15) == 0;
-  for (int d = 0; d < last && vec; ++d)
-    if (u.dstride[d] % VV != 0) vec = false;
-  if (vec) {
-    hipLaunchKernelGGL((sp_update_kernel<T, VV>), dim3(grid_for(n / VV)), dim3(SP_BLOCK), 0, st, d_dst, d_src,
-                       d_mask, u, n / VV);
-  } else {
-    hipLaunchKernelGGL((sp_update_kernel<T, 1>), dim3(grid_for(n)), dim3(SP_BLOCK), 0, st, d_dst, d_src,
-                       d_mask, u, n);
-  }
-  SP_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int sp_update(void* d_dst, int32_t dst_dtype, const int64_t* dst_shape, int32_t ndim,
-                         const int64_t* ul, const int64_t* lr, const void* d_src, int32_t src_dtype,
-                         int32_t reducer, int32_t mask_mode, uint8_t* d_mask, void* stream) {
+// What one sp_update call launches: the ONE place that decides it, used by the launch and by the query
+// sp_update_path.  `cls` = the compute class (sp_merge_class: SP_F16 is float arithmetic rounded to half, SP_F32,
+// SP_F64, SP_I64), `vec` = elements per thread step (the class's V when the box's innermost extent, the box origin,
+// every outer stride of the tile and both pointers allow it, else 1; 0 for an empty box: nothing is launched).
+// Host code only: no pointer is dereferenced.
+static int sp_update_choose(const void* d_dst, int32_t dst_dtype, const int64_t* dst_shape, int32_t ndim,
+                            const int64_t* ul, const int64_t* lr, const void* d_src, int32_t src_dtype, UpdDesc* desc,
+                            int64_t* count, int32_t* cls_out, int32_t* vec_out) {
   if (ndim < 0 || ndim > SP_MAX_DIMS) SP_FAIL("sp_update: ndim=%d unsupported (max %d)", ndim, SP_MAX_DIMS);
   if (!d_dst || !d_src) SP_FAIL("sp_update: NULL pointer");
   if (dst_dtype < 0 || dst_dtype >= SP_DTYPE_COUNT || src_dtype < 0 || src_dtype >= SP_DTYPE_COUNT)
     SP_FAIL("sp_update: bad dtype");
-  if (reducer < SP_REDUCER_NONE || reducer > SP_REDUCER_OR) SP_FAIL("sp_update: bad reducer %d", reducer);
-  if (mask_mode < SP_MASK_ALL_CLEAR || mask_mode > SP_MASK_ARRAY) SP_FAIL("sp_update: bad mask_mode");
-  if (mask_mode == SP_MASK_ARRAY && !d_mask) SP_FAIL("sp_update: SP_MASK_ARRAY needs d_mask");
-  UpdDesc u;
+  if (ndim > 0 && (!dst_shape || !ul || !lr)) SP_FAIL("sp_update: NULL shape / box");
+  UpdDesc& u = *desc;
   memset(&u, 0, sizeof(u));
   u.dst_dtype = dst_dtype;
   u.src_dtype = src_dtype;
-  u.reducer = reducer;
-  u.mask_mode = mask_mode;
   int64_t n = 1;
   if (ndim == 0) {
     // zero-dimensional tile (tile.pyx:212-217): a single cell
@@ -482,15 +514,70 @@ extern "C" int sp_update(void* d_dst, int32_t dst_dtype, const int64_t* dst_shap
       n *= u.box[d];
     }
   }
-  if (n == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
   const int cls = sp_merge_class(dst_dtype, src_dtype);
   u.round_f16 = cls == SP_F16 ? 1 : 0;
+  *count = n;
+  *cls_out = cls;
+  *vec_out = 0;
+  if (n == 0) return 0;
+  const int VV = (cls == SP_F16 || cls == SP_F32) ? sp_cls<float>::V : (cls == SP_F64 ? sp_cls<double>::V : sp_cls<int64_t>::V);
+  const int last = u.ndim - 1;
+  bool vec = (u.box[last] % VV == 0) && (u.doff % VV == 0) &&
+             ((((uintptr_t)d_dst) | ((uintptr_t)d_src)) & 15) == 0;
+  for (int d = 0; d < last && vec; ++d)
+    if (u.dstride[d] % VV != 0) vec = false;
+  *vec_out = vec ? VV : 1;
+  return 0;
+}
+
+extern "C" int sp_update_path(const void* d_dst, int32_t dst_dtype, const int64_t* dst_shape, int32_t ndim,
+                              const int64_t* ul, const int64_t* lr, const void* d_src, int32_t src_dtype,
+                              int32_t* compute_class, int32_t* vector_width) {
+  UpdDesc u;
+  int64_t n;
+  int32_t cls = 0, vec = 0;
+  if (sp_update_choose(d_dst, dst_dtype, dst_shape, ndim, ul, lr, d_src, src_dtype, &u, &n, &cls, &vec)) return 1;
+  if (compute_class) *compute_class = cls;
+  if (vector_width) *vector_width = vec;
+  return 0;
+}
+
+template <typename T>
+static int sp_update_launch(void* d_dst, const void* d_src, uint8_t* d_mask, const UpdDesc& u, int64_t n, int32_t vec,
+                            hipStream_t st) {
+  constexpr int VV = sp_cls<T>::V;
+  if (vec == VV) {
+    hipLaunchKernelGGL((sp_update_kernel<T, VV>), dim3(grid_for(n / VV)), dim3(SP_BLOCK), 0, st, d_dst, d_src,
+                       d_mask, u, n / VV);
+  } else if (vec == 1) {
+    hipLaunchKernelGGL((sp_update_kernel<T, 1>), dim3(grid_for(n)), dim3(SP_BLOCK), 0, st, d_dst, d_src,
+                       d_mask, u, n);
+  } else {
+    SP_FAIL("sp_update: no kernel of vector width %d for this class", vec);
+  }
+  SP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sp_update(void* d_dst, int32_t dst_dtype, const int64_t* dst_shape, int32_t ndim,
+                         const int64_t* ul, const int64_t* lr, const void* d_src, int32_t src_dtype,
+                         int32_t reducer, int32_t mask_mode, uint8_t* d_mask, void* stream) {
+  UpdDesc u;
+  int64_t n;
+  int32_t cls = 0, vec = 0;
+  if (sp_update_choose(d_dst, dst_dtype, dst_shape, ndim, ul, lr, d_src, src_dtype, &u, &n, &cls, &vec)) return 1;
+  if (reducer < SP_REDUCER_NONE || reducer > SP_REDUCER_OR) SP_FAIL("sp_update: bad reducer %d", reducer);
+  if (mask_mode < SP_MASK_ALL_CLEAR || mask_mode > SP_MASK_ARRAY) SP_FAIL("sp_update: bad mask_mode");
+  if (mask_mode == SP_MASK_ARRAY && !d_mask) SP_FAIL("sp_update: SP_MASK_ARRAY needs d_mask");
+  u.reducer = reducer;
+  u.mask_mode = mask_mode;
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
   switch (cls) {
     case SP_F16:
-    case SP_F32: return sp_update_launch<float>(d_dst, d_src, d_mask, u, n, st);
-    case SP_F64: return sp_update_launch<double>(d_dst, d_src, d_mask, u, n, st);
-    default: return sp_update_launch<int64_t>(d_dst, d_src, d_mask, u, n, st);
+    case SP_F32: return sp_update_launch<float>(d_dst, d_src, d_mask, u, n, vec, st);
+    case SP_F64: return sp_update_launch<double>(d_dst, d_src, d_mask, u, n, vec, st);
+    default: return sp_update_launch<int64_t>(d_dst, d_src, d_mask, u, n, vec, st);
   }
 }
 

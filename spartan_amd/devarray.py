@@ -230,6 +230,31 @@ def _prod(shape):
   return n
 
 
+def element_span(a):
+  """[lo, hi): the range of element offsets in its storage that the view `a` touches (None for an empty view)."""
+  lo = hi = a.offset
+  for n, s in zip(a.shape, a.strides):
+    if n == 0:
+      return None
+    if s > 0:
+      hi += (n - 1) * s
+    else:
+      lo += (n - 1) * s
+  return lo, hi + 1
+
+
+def may_overlap(a, b):
+  """Do the views `a` and `b` share a storage and do the byte ranges they span intersect?  (Spans, not cells: two
+  interleaved step-2 views count as overlapping.  The answer "no" is what a kernel with a no-overlap precondition
+  needs.)"""
+  if getattr(a, 'storage', None) is None or a.storage is not getattr(b, 'storage', None):
+    return False
+  sa, sb = element_span(a), element_span(b)
+  if sa is None or sb is None:
+    return False
+  return sa[0] * a.dtype.itemsize < sb[1] * b.dtype.itemsize and sb[0] * b.dtype.itemsize < sa[1] * a.dtype.itemsize
+
+
 def _view_reshape(shape, strides, new_shape):
   """Strides of `new_shape` over the same memory, or None if the reshape needs a copy (NumPy's no-copy rule:
   walk both shapes, a group of old axes can be re-cut iff it is contiguous within itself)."""

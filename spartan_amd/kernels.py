@@ -174,6 +174,31 @@ def slice_copy(dst, dst_offset, dst_strides, src, src_offset, src_strides, shape
   return dst
 
 
+def slice_copy_path(dst_ptr, dst_strides, src_ptr, src_strides, shape, elem_size):
+  """Which kernel slice_copy would launch for a box at these ADDRESSES (integers; host code, nothing is read or
+  launched): (bytes one thread step moves -- the element size, 16 when widened, 0 for an empty box --, whether the
+  LDS-tiled transpose kernel is taken).  Raises what the launch would raise."""
+  word, transpose = C.c_int32(0), C.c_int32(0)
+  check(_hip.lib().sp_slice_copy_path(
+      C.c_void_p(int(dst_ptr)), _hip.i64_array(dst_strides), C.c_void_p(int(src_ptr)), _hip.i64_array(src_strides),
+      _hip.i64_array(shape), len(shape), int(elem_size), C.byref(word), C.byref(transpose)))
+  return word.value, bool(transpose.value)
+
+
+_MERGE_CLASS = {_hip.SP_F16: 'half', _hip.SP_F32: 'float', _hip.SP_F64: 'double', _hip.SP_I64: 'int64'}
+
+
+def update_path(dst_ptr, dst_dtype, dst_shape, ul, lr, src_ptr, src_dtype):
+  """Which kernel update would launch for a tile and an update at these ADDRESSES (integers; host code, nothing is
+  read or launched): (compute class -- 'half' (float arithmetic rounded to half), 'float', 'double' or 'int64' --,
+  elements per thread step: 4, 2 or 1, 0 for an empty box).  Raises what the launch would raise."""
+  cls, vec = C.c_int32(0), C.c_int32(0)
+  check(_hip.lib().sp_update_path(
+      C.c_void_p(int(dst_ptr)), _hip.sp_dtype(dst_dtype), _hip.i64_array(dst_shape), len(dst_shape), _hip.i64_array(ul),
+      _hip.i64_array(lr), C.c_void_p(int(src_ptr)), _hip.sp_dtype(src_dtype), C.byref(cls), C.byref(vec)))
+  return _MERGE_CLASS[cls.value], vec.value
+
+
 class GemmImages(object):
   """One fp32 GEMM operand cut into the split tier's bf16 images (gemm_prepare): `buf` holds the operand's own window
   flag and the three images of all `img_rows` rows; the handle stands for rows [row0, row0 + rows) of them.  `event`
