@@ -50,8 +50,20 @@
 // into C is not built: 32768^3 would need seven).
 //
 // MAINLOOP (sp_gemm_glds_kernel_bf16x3).  256 x (64 WN) workgroup tile, 2 x WN waves of 128 x 64 each (the k-means
-// split kernel's geometry), k-tiles of 16 brought by global_load_lds_dwordx4 into two LDS stages, the pieces of a
-// request spread over the MFMAs of the k-step before; 18 ds_read_b128 fragment reads and 48 MFMAs per wave and k-step.
+// split kernel's geometry), k-tiles of 16 brought by global_load_lds_dwordx4 into two LDS stages; 18 ds_read_b128
+// fragment reads and 48 MFMAs per wave and k-step.  The loop is software-pipelined one k-tile ahead IN REGISTERS: the
+// MFMAs of k-tile t take every operand from VGPRs that were filled during k-tile t - 1, so no LDS latency stands
+// between the barrier and the first MFMA.  During k-tile t a wave
+//   * issues the 48 MFMAs of tile t (term order and (i, j) walk as ever: the bits of C do not depend on the pipeline);
+//   * reads the 18 fragments of tile t + 1 from stage (t + 1) & 1, one per MFMA gap: hi into a second register set
+//     (the hi fragments are live to the last term), lo and mid into the registers of tile t as the term order frees
+//     them (al after term 0, bl after 1, am after 3, bm after 4) -- 24 VGPRs more than without the pipeline;
+//   * issues the six pieces of tile t + 2 into stage t & 1, one after every fourth MFMA of the first half;
+// then waits for its pieces (vmcnt) AND its fragment reads (lgkmcnt) and meets the others at the one barrier per
+// k-tile.  That barrier publishes tile t + 2 and tells every wave that stage (t + 1) & 1 has been read, so the pieces
+// of tile t + 3 may overwrite it.  The loop is unrolled by two so that stages and register sets are constants; the
+// last tile but one issues no pieces, the last one no reads either.  The reads are asm with tied destinations (see
+// GS_READ_A).
 // An LDS image is [row][2 chunks of 16 B]; chunk q of row r lives in slot q ^ ((r >> 4) & 1): a ds_read_b128 is served
 // in groups of 16 lanes -- rows {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of a fragment's 32 -- and the banks repeat
 // every 8 rows of 32 B, so inside a group the rows below 16 and the rows from 16 on that share their banks are sent
@@ -82,6 +94,11 @@ struct GsCfg {
   static constexpr int SLOTS = SP_CUS * (WN == 4 ? 1 : 2);              // resident workgroups
   static_assert(APW >= 1 && BPW >= 1 && APW * NW * 1024 == A_BYTES && BPW * NW * 1024 == B_BYTES, "tile / waves mismatch");
   static_assert(NPIECES * 4 <= 48, "one piece after every fourth MFMA");
+};
+
+template <int V>
+struct GsInt {                                    // a constant handed to a generic lambda
+  static constexpr int value = V;
 };
 
 __device__ __forceinline__ bool gs_outside(float v) {
@@ -245,6 +262,77 @@ __global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf1
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+  // fragments: row (wave tile row + l31 [+ 32 i]), slot lh ^ ((row >> 4) & 1)
+  const int fslot = (lh ^ ((l31 >> 4) & 1)) * 16;
+  const int a_frag = (wm * 128 + l31) * GS_RB + fslot;
+  const int b_frag = 3 * G::A_BYTES + (wn * 64 + l31) * GS_RB + fslot;
+  const unsigned a_rd[2] = {s_base + (unsigned)a_frag, s_base + (unsigned)(G::STAGE_BYTES + a_frag)};   // per stage
+  const unsigned b_rd[2] = {s_base + (unsigned)b_frag, s_base + (unsigned)(G::STAGE_BYTES + b_frag)};
+
+  // The fragments of k-tile t: mid and lo in one set of registers, which tile t + 1 refills as the term order frees
+  // them; hi is live to the last term, so it has two sets and tile t uses set t & 1.
+  gs_bf16x8 am[4], al[4], bm[2], bl[2], ah[2][4], bh[2][2];
+  // A fragment read, image p_ (0 hi, 1 mid, 2 lo) of stage s_, into `dst`.  Written in asm with the destination tied
+  // ("+v"): the new fragment goes into the very registers of the old one, which hipcc's allocator does not find by
+  // itself (it took fresh registers for the next tile and spilled).  The compiler then does not count these reads in
+  // lgkmcnt, so GS_READS_DONE states the wait, and passes every fragment through it: no MFMA that takes one can be
+  // moved in front of the wait.
+#define GS_READ_A(dst, s_, p_, i_) \
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(a_rd[s_]), "n"((p_) * G::A_BYTES + (i_) * 32 * GS_RB) : "memory")
+#define GS_READ_B(dst, s_, p_, j_) \
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(b_rd[s_]), "n"((p_) * G::B_BYTES + (j_) * 32 * GS_RB) : "memory")
+#define GS_READS_DONE(s_)                                                                                             \
+  do {                                                                                                                \
+    asm volatile("s_waitcnt lgkmcnt(0)"                                                                               \
+                 : "+v"(al[0]), "+v"(al[1]), "+v"(al[2]), "+v"(al[3]), "+v"(am[0]), "+v"(am[1]), "+v"(am[2]),          \
+                   "+v"(am[3]), "+v"(bl[0]), "+v"(bl[1]), "+v"(bm[0]), "+v"(bm[1])                                     \
+                 :: "memory");                                                                                        \
+    asm volatile("" : "+v"(ah[s_][0]), "+v"(ah[s_][1]), "+v"(ah[s_][2]), "+v"(ah[s_][3]), "+v"(bh[s_][0]),             \
+                      "+v"(bh[s_][1]) :: "memory");                                                                   \
+  } while (0)
+
+  // One k-tile: its 48 MFMAs -- al bh, ah bl, am bm, am bh, ah bm, ah bh for the 4 x 2 tiles of the wave -- from
+  // registers alone.  In the gaps between them, if `rd`, the 18 fragment reads of tile t + 1 from stage (t + 1) & 1
+  // (at most one per gap: hi into the other set first, then lo and mid behind the last MFMA that reads the registers
+  // they go to; the last one 6 MFMAs before the end), and if `ld`, a piece of the request for tile t + 2 into stage
+  // t & 1 after every fourth.  `par` is t & 1 as a constant: stages and register sets are then fixed per copy of the
+  // body, and nothing is moved between the sets.
+  auto ktile = [&](auto par_, const bool rd, const bool ld, int t) __attribute__((always_inline)) {
+    constexpr int CUR = decltype(par_)::value, NXT = CUR ^ 1;
+    const int64_t ka_ = (int64_t)(t + 2) * a_slab, kb_ = (int64_t)(t + 2) * b_slab;
+    const unsigned st_ = s_base + (unsigned)CUR * G::STAGE_BYTES;
+#pragma unroll
+    for (int idx = 0; idx < 48; ++idx) {
+      const int term = idx >> 3, i = (idx & 7) >> 1, j = idx & 1;
+      const gs_bf16x8 a = term == 0 ? al[i] : (term == 2 || term == 3) ? am[i] : ah[CUR][i];
+      const gs_bf16x8 b = term == 1 ? bl[j] : (term == 2 || term == 4) ? bm[j] : bh[CUR][j];
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (rd) {
+        const int q = idx & 7, r = q < 3 ? q : q - 1;          // gaps 0 1 2 4 [5 6] of a term; 3 and 7 may hold a piece
+        if (term == 0 && q != 3 && q != 7) {
+          if (r < 4) GS_READ_A(ah[NXT][r & 3], NXT, 0, r & 3);
+          else GS_READ_B(bh[NXT][r & 1], NXT, 0, r & 1);
+        }
+        if (term == 1 && q != 3 && r < 4) GS_READ_A(al[r & 3], NXT, 2, r & 3);      // al: free after term 0
+        if (term == 2 && q < 2) GS_READ_B(bl[q & 1], NXT, 2, q & 1);                // bl: after term 1
+        if (term == 4 && q < 4) GS_READ_A(am[q & 3], NXT, 1, q & 3);                // am: after term 3
+        if (term == 5 && q < 2) GS_READ_B(bm[q & 1], NXT, 1, q & 1);                // bm: after term 4
+      }
+      if (ld && idx % 4 == 3 && idx / 4 < NPIECES) GS_PIECE(idx / 4);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (ld) SP_GLDS_LANDED();
+    if (rd) GS_READS_DONE(NXT);
+    // tile t + 2 has landed in stage t & 1, and this wave's reads of stage (t + 1) & 1 have returned, before any
+    // wave's pieces for tile t + 3 may overwrite it
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  GsInt<0> even;
+  GsInt<1> odd;
+
+  // prologue: tile 0 lands and is published; tile 1's request goes out whole; tile 0's fragments are read
   {
     const int64_t ka_ = 0, kb_ = 0;
     const unsigned st_ = s_base;
@@ -253,44 +341,40 @@ __global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf1
   }
   SP_GLDS_LANDED();
   __syncthreads();
-
-  // fragments: row (wave tile row + l31 [+ 32 i]), slot lh ^ ((row >> 4) & 1)
-  const int fslot = (lh ^ ((l31 >> 4) & 1)) * 16;
-  const int a_frag = (wm * 128 + l31) * GS_RB + fslot;
-  const int b_frag = 3 * G::A_BYTES + (wn * 64 + l31) * GS_RB + fslot;
-
-  for (int t = 0; t < KT; ++t) {
-    const bool more = t + 1 < KT;
-    const int64_t ka_ = (int64_t)(t + 1) * a_slab, kb_ = (int64_t)(t + 1) * b_slab;
-    const unsigned st_ = s_base + (unsigned)((t + 1) & 1) * G::STAGE_BYTES;
-    const char* st = gs_smem + (t & 1) * G::STAGE_BYTES;
-    gs_bf16x8 af[3][4], bf[3][2];
+  if (KT > 1) {
+    const int64_t ka_ = a_slab, kb_ = b_slab;
+    const unsigned st_ = s_base + G::STAGE_BYTES;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[p][i] = *(const gs_bf16x8*)(st + p * G::A_BYTES + a_frag + i * 32 * GS_RB);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bf[p][j] = *(const gs_bf16x8*)(st + p * G::B_BYTES + b_frag + j * 32 * GS_RB);
-    }
-    // 48 MFMAs: al bh, ah bl, am bm, am bh, ah bm, ah bh for the 4 x 2 tiles of the wave; a piece of the next
-    // k-tile's request after every fourth
-    int piece = 0;
-#pragma unroll
-    for (int idx = 0; idx < 48; ++idx) {
-      const int term = idx >> 3, i = (idx & 7) >> 1, j = idx & 1;
-      const int pa = term == 0 ? 2 : (term == 2 || term == 3) ? 1 : 0;
-      const int pb = term == 1 ? 2 : (term == 2 || term == 4) ? 1 : 0;
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[pa][i], bf[pb][j], acc[i][j], 0, 0, 0);
-      if (idx % 4 == 3 && piece < NPIECES) {
-        __builtin_amdgcn_sched_barrier(0);
-        if (more) GS_PIECE(piece);
-        __builtin_amdgcn_sched_barrier(0);
-        ++piece;
-      }
-    }
-    if (more) SP_GLDS_LANDED();
-    __syncthreads();      // tile t+1 has landed and every wave is done reading stage t
+    for (int i = 0; i < NPIECES; ++i) GS_PIECE(i);
   }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ah[0][i] = ah[1][i] = am[i] = al[i] = gs_bf16x8{};
+    GS_READ_A(ah[0][i], 0, 0, i);
+    GS_READ_A(am[i], 0, 1, i);
+    GS_READ_A(al[i], 0, 2, i);
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    bh[0][j] = bh[1][j] = bm[j] = bl[j] = gs_bf16x8{};
+    GS_READ_B(bh[0][j], 0, 0, j);
+    GS_READ_B(bm[j], 0, 1, j);
+    GS_READ_B(bl[j], 0, 2, j);
+  }
+  SP_GLDS_LANDED();
+  GS_READS_DONE(0);
+  __syncthreads();
+
+  // two k-tiles per trip, then the last one of an odd count
+  int t = 0;
+  for (; t + 1 < KT; t += 2) {
+    ktile(even, true, t + 2 < KT, t);
+    ktile(odd, t + 2 < KT, t + 3 < KT, t + 1);
+  }
+  if (t < KT) ktile(even, false, false, t);
+#undef GS_READ_A
+#undef GS_READ_B
+#undef GS_READS_DONE
 #undef GS_PIECE
 
   // ---- epilogue (as sp_gemm_glds_kernel's): C/D layout col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
