@@ -44,6 +44,7 @@ _NP2SP = {
 NARROW = frozenset(np.dtype(t) for t in (np.int8, np.int16, np.uint16, np.uint32, np.float16))
 SUPPORTED = 'float32 float64 int32 int64 bool uint8 int8 int16 uint16 uint32 float16'
 _SP2NP = {v: k for k, v in _NP2SP.items()}
+FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
 
 
 def sp_dtype(dt):
@@ -70,7 +71,7 @@ def refuse_not_float(dt, what):
   """The loud refusal of a kernel that exists in float32 and float64 only (the dense factorisation and eigenvalue
   kernels)."""
   dt = np.dtype(dt)
-  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+  if dt not in FLOATS:
     raise TypeError('dtype %s is not supported by %s of the HIP tile backend (supported: float32 float64); convert '
                     'with astype first' % (dt, what))
 
@@ -356,111 +357,13 @@ SP_NB_MAX_LABELS = 128   # of spartan_hip_nb.h
 SP_AFF_METRICS = {'rbf': 0, 'euclidean': 1, 'manhattan': 2}   # SP_AFF_* of spartan_hip_spectral.h
 
 
-def check_affinity_params(metric, gamma, what='affinity'):
-  """(the library's code of `metric`, gamma as a float), or what sp_affinity_* refuses: NotImplementedError for
-  'scaled_euclidean', ValueError for an unknown metric or a gamma that is not finite.  The one copy: the launchers, the
-  backend and the NumPy bodies of examples/_spectral.py all refuse through it."""
-  if metric == 'scaled_euclidean':
-    raise NotImplementedError("%s: 'scaled_euclidean' is refused: the reference calls np.square(X, Y), which writes X "
-                              "squared INTO its second operand, so its result depends on the order in which the pairs "
-                              "are visited" % what)
-  if metric not in SP_AFF_METRICS:
-    raise ValueError('%s: unknown metric %r (%s)' % (what, metric, ' '.join(sorted(SP_AFF_METRICS))))
-  gamma = float(gamma)
-  if gamma != gamma or gamma in (float('inf'), float('-inf')):
-    raise ValueError('%s: gamma = %r must be finite' % (what, gamma))
-  return SP_AFF_METRICS[metric], gamma
-
-
-def check_nb_operands(x_dtype, x_shape, labels_dtype, labels_shape, label_size, what='nb_step'):
-  """(m, d, label_size) of the operands of a naive Bayes step, or what sp_nb_step refuses: TypeError for data that is
-  not float32 / float64 or labels that are not int64, ValueError for label_size outside 1 .. 128, data that is not 2-D
-  or labels that are not [m] or [m, 1].  The one copy: the launcher, the backend and the NumPy body of examples/_nb.py
-  all refuse through it."""
-  if np.dtype(x_dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
-    raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, np.dtype(x_dtype)))
-  if np.dtype(labels_dtype) != np.dtype(np.int64):
-    raise TypeError('%s: labels of dtype %s; convert with astype(int64) first' % (what, np.dtype(labels_dtype)))
-  label_size = int(label_size)
-  if not 1 <= label_size <= SP_NB_MAX_LABELS:
-    raise ValueError('%s: label_size = %d must be in 1 .. %d' % (what, label_size, SP_NB_MAX_LABELS))
-  x_shape, labels_shape = tuple(int(v) for v in x_shape), tuple(int(v) for v in labels_shape)
-  if len(x_shape) != 2:
-    raise ValueError('%s: expected data of shape (m, d), got %s' % (what, x_shape))
-  if labels_shape not in ((x_shape[0],), (x_shape[0], 1)):
-    raise ValueError('%s: labels of shape %s for %d rows' % (what, labels_shape, x_shape[0]))
-  return x_shape[0], x_shape[1], label_size
-
-
-def check_nbody_operands(dtypes, shapes, r0, m, g, rmin, splits=0, what='nbody_accel'):
-  """(dtype, n, r0, m, g, rmin, splits) of an all-pairs gravity call on x, y, z and mass -- `dtypes` and `shapes` are
-  theirs, in that order -- or what sp_nbody_accel refuses: TypeError ("astype first") for arrays that are not float32 /
-  float64 or that are of two dtypes; ValueError for arrays that are not 1-D and of equal length, targets r0 .. r0 + m
-  that are not among the n bodies, splits < 0, a g that is not finite in the arrays' dtype and an rmin that is not
-  finite and > 0 in it.  The one copy: the launcher, the backend, the NumPy body of examples/_nbody.py and the driver
-  all refuse through it."""
-  dtypes = [np.dtype(d) for d in dtypes]
-  for d in dtypes:
-    if d not in (np.dtype(np.float32), np.dtype(np.float64)):
-      raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, d))
-  for d in dtypes[1:]:
-    if d != dtypes[0]:
-      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, dtypes[0], d))
-  shapes = [tuple(int(v) for v in s) for s in shapes]
-  if any(len(s) != 1 for s in shapes) or any(s != shapes[0] for s in shapes):
-    raise ValueError('%s: x, y, z and mass must be 1-D and of equal length, got shapes %s' % (what, shapes))
-  n, r0, m, splits = shapes[0][0], int(r0), int(m), int(splits)
-  if r0 < 0 or m < 0 or r0 + m > n:
-    raise ValueError('%s: bodies %d .. %d are not among the %d' % (what, r0, r0 + m, n))
-  if splits < 0:
-    raise ValueError('%s: splits = %d' % (what, splits))
-  g, rmin = float(g), float(rmin)
-  with np.errstate(all='ignore'):
-    gt, rt = dtypes[0].type(g), dtypes[0].type(rmin)
-  if not np.isfinite(gt):
-    raise ValueError('%s: g = %r must be finite in %s' % (what, g, dtypes[0]))
-  if not (rt > 0 and np.isfinite(rt)):
-    raise ValueError('%s: rmin = %r must be finite and > 0 in %s' % (what, rmin, dtypes[0]))
-  return dtypes[0], n, r0, m, g, rmin, splits
-
-
-def check_item_topk_operands(dtypes, t_shape, tnorm_shape, s_shape, snorm_shape, k, splits=0, what='item_topk'):
-  """(dtype, users, m, ns, k, splits) of a cosine top-k call on targets [users, m], tnorm [m], sources [users, ns] and
-  snorm [ns] -- `dtypes` are theirs, in that order -- or what sp_item_topk refuses: TypeError ("astype first") for
-  operands that are not float32 / float64 or that are of two dtypes; ValueError for targets or sources that are not 2-D,
-  user counts that differ, norms that are not [m] and [ns], a k outside 1 .. CF_MAX_K and splits < 0.  The one copy:
-  the launcher, the backend, the NumPy body of examples/cf/_cf.py and the driver all refuse through it."""
-  dtypes = [np.dtype(d) for d in dtypes]
-  for d in dtypes:
-    if d not in (np.dtype(np.float32), np.dtype(np.float64)):
-      raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, d))
-  for d in dtypes[1:]:
-    if d != dtypes[0]:
-      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, dtypes[0], d))
-  t_shape, s_shape = tuple(int(v) for v in t_shape), tuple(int(v) for v in s_shape)
-  tnorm_shape, snorm_shape = tuple(int(v) for v in tnorm_shape), tuple(int(v) for v in snorm_shape)
-  if len(t_shape) != 2 or len(s_shape) != 2:
-    raise ValueError('%s: targets and sources must be 2-D [users, items], got shapes %s and %s' % (what, t_shape, s_shape))
-  if t_shape[0] != s_shape[0]:
-    raise ValueError('%s: targets of %d users against sources of %d' % (what, t_shape[0], s_shape[0]))
-  if tnorm_shape != (t_shape[1],) or snorm_shape != (s_shape[1],):
-    raise ValueError('%s: norms of shapes %s and %s for %d targets and %d sources'
-                     % (what, tnorm_shape, snorm_shape, t_shape[1], s_shape[1]))
-  k, splits = int(k), int(splits)
-  if not 1 <= k <= CF_MAX_K:
-    raise ValueError('%s: k = %d is outside 1 .. %d' % (what, k, CF_MAX_K))
-  if splits < 0:
-    raise ValueError('%s: splits = %d is negative' % (what, splits))
-  return dtypes[0], t_shape[0], t_shape[1], s_shape[1], k, splits
-
-
 _extras = None
 
 
 def extras():
-  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn, apsp, als_solve, fuzzy_step, lda_step,
-  affinity_degree / affinity_matrix, nb_step, nbody_accel, item_topk);
-  raises if it has not been built."""
+  """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn / knn_merge, apsp / graph_from_knn,
+  als_solve, fuzzy_step, lda_step, affinity_degree / affinity_matrix, nb_step, nbody_accel, item_topk / item_topk_merge);
+  raises if it has not been built.  What their Python side refuses: tile_checks.py."""
   global _extras
   if _extras is None:
     lib()

@@ -21,6 +21,7 @@ from . import _hip, kernels, lower
 from . import devarray as D
 from . import sparse as sparse_mod
 from .array import distarray, tile
+from .backend_hip_extras import ExtrasTileBodies
 from .expr.local import LocalMapLocationExpr, FnCallExpr, LocalInput
 from .program import ProgramTooLarge, class_of, join_class
 
@@ -390,7 +391,7 @@ def _no_copy(t):
   raise lower.NotLowerable('an operand the kernels cannot address in place')
 
 
-class HipBackend(object):
+class HipBackend(ExtrasTileBodies):
   name = 'hip'
 
   def __init__(self, device=None):
@@ -1283,408 +1284,6 @@ class HipBackend(object):
     vals, idx = kernels.sort_rows(lines.reshape(outer * inner, n), values=not indices, indices=indices)
     out = (idx if indices else vals).reshape(outer, inner, n)
     return self.contiguous(out.movedim(2, 1)).reshape(shape)
-
-  def potrf(self, t):
-    """scipy.linalg.lapack.potrf(t, lower=1, clean=1)[0] as a NEW tensor: the Cholesky factor L of the symmetric
-    positive definite fp32 / fp64 matrix `t` (its lower triangle is read), zero above the diagonal (sp_potrf;
-    examples/cholesky.py:9-13).  numpy.linalg.LinAlgError, with LAPACK's words, if a leading minor is not positive
-    definite -- learnt from one 4-byte copy to the host, the only point at which this call waits for the device."""
-    t = self._as_device(t)
-    dt = self.dtype_of(t)
-    _hip.refuse_not_float(dt, 'potrf')
-    if t.dim() != 2 or t.shape[0] != t.shape[1]:
-      raise ValueError('potrf: expected a square matrix, got shape %s' % (tuple(t.shape),))
-    out = self.copy(t)           # (a strided view becomes contiguous here; the input is never written)
-    if t.shape[0] == 0:
-      return out
-    info = self.empty((1,), np.int32)
-    self.launches += 1
-    kernels.potrf(out, info)
-    order = int(info.numpy()[0])
-    if order:
-      raise np.linalg.LinAlgError('%d-th leading minor of the array is not positive definite' % order)
-    return out
-
-  def trsm_rlt(self, b, l):
-    """x with x . l^T = b as a NEW tensor: `l` [n, n] lower triangular, `b` [m, n] (sp_trsm_rlt) -- scipy's
-    dtrtrs(l, b.T, lower=1)[0].T (examples/cholesky.py:16-20), b . inv(l.T) without the inverse (ssvd/qr.py:40-43)."""
-    b, l = self._as_device(b), self._as_device(l)
-    for t in (b, l):
-      _hip.refuse_not_float(self.dtype_of(t), 'trsm_rlt')
-    if self.dtype_of(b) != self.dtype_of(l):
-      raise TypeError('trsm_rlt: operands of two dtypes (%s, %s); convert with astype first'
-                      % (self.dtype_of(b), self.dtype_of(l)))
-    if b.dim() != 2 or l.dim() != 2 or l.shape[0] != l.shape[1] or b.shape[1] != l.shape[0]:
-      raise ValueError('trsm_rlt: shapes %s and %s do not fit' % (tuple(b.shape), tuple(l.shape)))
-    out = self.copy(b)
-    if out.numel():
-      self.launches += 1
-      kernels.trsm_rlt(out, self.contiguous(l))
-    return out
-
-  def syev(self, t):
-    """(w, V) as NEW tensors: the eigenvalues of the symmetric fp32 / fp64 matrix `t` in ascending order and the
-    eigenvectors as the columns of V, t . V = V . diag(w) (sp_syevj, two-sided Jacobi; LAPACK's syevd(t, lower=1): the
-    lower triangle of `t` is read, `t` is not written).  numpy.linalg.LinAlgError if 64 sweeps do not converge (a NaN
-    in `t`).  Waits for the device once per sweep (one word) and once for info; self.syev_sweeps holds the number of
-    sweeps of the last call."""
-    t = self._as_device(t)
-    dt = self.dtype_of(t)
-    _hip.refuse_not_float(dt, 'syev')
-    if t.dim() != 2 or t.shape[0] != t.shape[1]:
-      raise ValueError('syev: expected a square matrix, got shape %s' % (tuple(t.shape),))
-    n = int(t.shape[0])
-    w, v = self.empty((n,), dt), self.empty((n, n), dt)
-    self.syev_sweeps = 0
-    if n == 0:
-      return w, v
-    if n > 1 and t.stride(1) != 1:
-      t = self.contiguous(t)
-    info = self.empty((1,), np.int32)
-    self.launches += 1
-    self.syev_sweeps = kernels.syevj(t, w, v, info)
-    if int(info.numpy()[0]):
-      raise np.linalg.LinAlgError('Eigenvalues did not converge')
-    return w, v
-
-  def _knn_rows(self, t):
-    """A 2-D operand of the knn kernels as a view with inner stride 1: the tensor itself where it is one (a row view
-    of a wider array included), a contiguous copy otherwise."""
-    rows_apart = t.shape[0] <= 1 or t.stride(0) >= t.shape[1]
-    return t if (t.shape[1] <= 1 or t.stride(1) == 1) and rows_apart else self.contiguous(t)
-
-  def knn(self, queries, points, k, index_offset=0, splits=0):
-    """(dist2, idx) as NEW tensors [nq, k]: for every row of `queries` [nq, d] the k rows of `points` [np, d] at the
-    smallest squared Euclidean distance sum_j (q_j - x_j)^2 (computed in that form, in the operands' precision),
-    ascending by (distance, index); idx (int64) = index_offset + row of `points`; +inf / -1 in the trailing slots when
-    np < k (sp_knn: distance and selection in one pass, nothing of size nq x np is written).  Both operands fp32 or
-    both fp64; 1 <= k <= 128.  splits: into how many ranges the points are cut (0: the library chooses); the result
-    does not depend on it, bit for bit."""
-    queries, points = self._as_device(queries), self._as_device(points)
-    dt = self.dtype_of(queries)
-    for t in (queries, points):
-      _hip.refuse_not_float(self.dtype_of(t), 'knn')
-    if dt != self.dtype_of(points):
-      raise TypeError('knn: operands of two dtypes (%s, %s); convert with astype first' % (dt, self.dtype_of(points)))
-    if queries.dim() != 2 or points.dim() != 2 or queries.shape[1] != points.shape[1]:
-      raise ValueError('knn: shapes %s and %s do not fit' % (tuple(queries.shape), tuple(points.shape)))
-    k = int(k)
-    if not 1 <= k <= _hip.KNN_MAX_K:
-      raise ValueError('knn: k = %d is outside 1 .. %d' % (k, _hip.KNN_MAX_K))
-    if int(splits) < 0:
-      raise ValueError('knn: splits = %d is negative' % int(splits))
-    nq = int(queries.shape[0])
-    dist2, idx = self.empty((nq, k), dt), self.empty((nq, k), np.int64)
-    if nq:
-      self.launches += 1
-      kernels.knn(self._knn_rows(queries), self._knn_rows(points), k, dist2, idx, index_offset, splits)
-    return dist2, idx
-
-  def knn_merge(self, cand_dist2, cand_idx, k):
-    """(dist2, idx) as NEW tensors [nq, k]: per row the k smallest by (distance, index) of the m candidates
-    (cand_dist2 fp32 / fp64, cand_idx int64, both [nq, m]); candidates with a negative index are padding, and so are
-    the trailing slots of the result (+inf / -1) when fewer than k are left (sp_knn_merge)."""
-    cand_dist2, cand_idx = self._as_device(cand_dist2), self._as_device(cand_idx)
-    dt = self.dtype_of(cand_dist2)
-    _hip.refuse_not_float(dt, 'knn_merge')
-    if self.dtype_of(cand_idx) != np.int64:
-      raise TypeError('knn_merge: candidate indices of dtype %s (int64 expected); convert with astype first'
-                      % (self.dtype_of(cand_idx),))
-    if cand_dist2.dim() != 2 or tuple(cand_dist2.shape) != tuple(cand_idx.shape):
-      raise ValueError('knn_merge: shapes %s and %s do not fit' % (tuple(cand_dist2.shape), tuple(cand_idx.shape)))
-    k = int(k)
-    if not 1 <= k <= _hip.KNN_MAX_K:
-      raise ValueError('knn_merge: k = %d is outside 1 .. %d' % (k, _hip.KNN_MAX_K))
-    nq = int(cand_dist2.shape[0])
-    dist2, idx = self.empty((nq, k), dt), self.empty((nq, k), np.int64)
-    if nq:
-      cand_dist2, cand_idx = self._knn_rows(cand_dist2), self._knn_rows(cand_idx)
-      if nq > 1 and cand_dist2.stride(0) != cand_idx.stride(0):      # (the kernel takes one row stride for both)
-        cand_dist2, cand_idx = self.contiguous(cand_dist2), self.contiguous(cand_idx)
-      self.launches += 1
-      kernels.knn_merge(cand_dist2, cand_idx, k, dist2, idx)
-    return dist2, idx
-
-  def item_topk(self, targets, tnorm, sources, snorm, k, index_offset=0, splits=0):
-    """(sim, idx) as NEW tensors [m, k]: for every column j of `targets` [users, m] the k columns i of `sources`
-    [users, ns] of the largest cosine similarity nan_to_num(dot_u(t[u][j], s[u][i]) / (tnorm[j] * snorm[i])), ordered
-    by (similarity descending, index ascending); idx (int64) = index_offset + column of `sources`; -inf / -1 in the
-    trailing slots when ns < k (sp_item_topk: similarity and selection in one pass, nothing of size m x ns is written;
-    include/spartan_hip_cf.h states the order of the arithmetic).  All four operands fp32 or all fp64; 1 <= k <= 128.
-    A target is not excluded from its own list.  splits: into how many ranges the sources are cut (0: the library
-    chooses); the result does not depend on it, nor on how the targets are banded, bit for bit.  Operands whose inner
-    stride is not 1 are first copied contiguous; two column ranges of one table are taken as they are.  The library
-    issues one kernel with one range and two with more (the second merges the ranges' candidates), and the call counts
-    as that many launches -- none when m = 0.  Refusals: _hip.check_item_topk_operands'."""
-    targets, tnorm, sources, snorm = (self._as_device(t) for t in (targets, tnorm, sources, snorm))
-    dt, users, m, ns, k, splits = _hip.check_item_topk_operands(
-        [self.dtype_of(t) for t in (targets, tnorm, sources, snorm)], targets.shape, tnorm.shape, sources.shape,
-        snorm.shape, k, splits)
-    before = self.launches
-    sim, idx = self.empty((m, k), dt), self.empty((m, k), np.int64)
-    if m:
-      kernels.item_topk(self._knn_rows(targets), self.contiguous(tnorm), self._knn_rows(sources), self.contiguous(snorm),
-                        k, sim, idx, index_offset, splits)
-      # (the library's choice of ranges, cf_ranges of csrc/cf.hip, to count its launches)
-      if ns <= 0:
-        ranges = 1
-      elif splits:
-        ranges = min(splits, ns)
-      else:
-        ranges = max(1, min(-(-512 // -(-m // 64)), -(-ns // max(4 * k, 64)), 64))
-        if ranges > 1:
-          ranges = -(-ns // (64 * -(-(-(-ns // ranges)) // 64)))
-      self.launches = before + (1 if ranges == 1 else 2)   # (a strided operand's copy belongs to the call)
-    return sim, idx
-
-  def item_topk_merge(self, cand_sim, cand_idx, k):
-    """(sim, idx) as NEW tensors [m, k]: per row the k best by (similarity descending, index ascending) of the
-    candidates (cand_sim fp32 / fp64, cand_idx int64, both [m, cands]); candidates with a negative index are padding,
-    and so are the trailing slots of the result (-inf / -1) when fewer than k are left (sp_item_topk_merge)."""
-    cand_sim, cand_idx = self._as_device(cand_sim), self._as_device(cand_idx)
-    dt = self.dtype_of(cand_sim)
-    _hip.refuse_not_float(dt, 'item_topk_merge')
-    if self.dtype_of(cand_idx) != np.int64:
-      raise TypeError('item_topk_merge: candidate indices of dtype %s (int64 expected); convert with astype first'
-                      % (self.dtype_of(cand_idx),))
-    if cand_sim.dim() != 2 or tuple(cand_sim.shape) != tuple(cand_idx.shape):
-      raise ValueError('item_topk_merge: shapes %s and %s do not fit' % (tuple(cand_sim.shape), tuple(cand_idx.shape)))
-    k = int(k)
-    if not 1 <= k <= _hip.CF_MAX_K:
-      raise ValueError('item_topk_merge: k = %d is outside 1 .. %d' % (k, _hip.CF_MAX_K))
-    m = int(cand_sim.shape[0])
-    sim, idx = self.empty((m, k), dt), self.empty((m, k), np.int64)
-    if m:
-      before = self.launches
-      cand_sim, cand_idx = self._knn_rows(cand_sim), self._knn_rows(cand_idx)
-      if m > 1 and cand_sim.stride(0) != cand_idx.stride(0):      # (the kernel takes one row stride for both)
-        cand_sim, cand_idx = self.contiguous(cand_sim), self.contiguous(cand_idx)
-      kernels.item_topk_merge(cand_sim, cand_idx, k, sim, idx)
-      self.launches = before + 1
-    return sim, idx
-
-  def apsp(self, t):
-    """The matrix of shortest-path lengths as a NEW tensor: `t` [n, n], fp32 / fp64, holds the edge lengths of a
-    directed graph (>= 0, +inf = no edge, the diagonal taken as 0; a symmetric `t` is an undirected graph); the result
-    has +inf where there is no path and 0 on the diagonal (sp_apsp: blocked Floyd-Warshall in the (min, +) semiring;
-    scipy.sparse.csgraph.shortest_path of the same weights, every path length the rounded sum of its edges).
-    ValueError if an off-diagonal entry is negative or NaN -- learnt from one 4-byte copy to the host, the only point
-    at which this call waits for the device."""
-    t = self._as_device(t)
-    dt = self.dtype_of(t)
-    _hip.refuse_not_float(dt, 'apsp')
-    if t.dim() != 2 or t.shape[0] != t.shape[1]:
-      raise ValueError('apsp: expected a square matrix, got shape %s' % (tuple(t.shape),))
-    before = self.launches
-    out = self.copy(t)           # (a strided view becomes contiguous here; the input is never written)
-    if t.shape[0] == 0:
-      return out
-    info = self.empty((1,), np.int32)
-    self.launches = before + 1   # (the call counts as one: the copy belongs to it)
-    kernels.apsp(out, info)
-    if int(info.numpy()[0]):
-      raise ValueError('apsp: negative or NaN edge length')
-    return out
-
-  def graph_from_knn(self, dist, idx):
-    """The dense undirected neighbour graph as a NEW tensor [n, n] of dist's dtype: +inf, 0 on the diagonal, and for
-    every pair (i, idx[i][e]) of the lists dist (fp32 / fp64, >= 0) and idx (int64), both [n, k], the smallest weight
-    stated for it in either direction, on both sides (sp_graph_from_knn); idx < 0 is padding.  What apsp takes."""
-    dist, idx = self._as_device(dist), self._as_device(idx)
-    dt = self.dtype_of(dist)
-    _hip.refuse_not_float(dt, 'graph_from_knn')
-    if self.dtype_of(idx) != np.int64:
-      raise TypeError('graph_from_knn: indices of dtype %s (int64 expected); convert with astype first'
-                      % (self.dtype_of(idx),))
-    if dist.dim() != 2 or tuple(dist.shape) != tuple(idx.shape):
-      raise ValueError('graph_from_knn: shapes %s and %s do not fit' % (tuple(dist.shape), tuple(idx.shape)))
-    n = int(dist.shape[0])
-    w = self.empty((n, n), dt)
-    if n:
-      dist, idx = self._knn_rows(dist), self._knn_rows(idx)
-      if n > 1 and dist.stride(0) != idx.stride(0):      # (the kernel takes one row stride for both)
-        dist, idx = self.contiguous(dist), self.contiguous(idx)
-      self.launches += 1
-      kernels.graph_from_knn(dist, idx, w)
-    return w
-
-  def als_solve(self, ratings, factors, la, alpha, implicit=False, info=None):
-    """One half-step of alternating least squares as a NEW tensor [m, f]: row i solves A_i x = b_i, built from row i of
-    `ratings` [m, n] and `factors` [n, f] (sp_als_solve: accumulation, Cholesky and substitution fused, per row).
-      explicit   A_i = sum_{r_ij != 0} y_j y_j^T + la |S_i| I,  b_i = sum r_ij y_j;  a row without ratings is exactly 0
-      implicit   A_i = Y^T Y + sum_j alpha r_ij y_j y_j^T + la I,  b_i = sum_{r_ij > 0} (1 + alpha r_ij) y_j
-    Both operands fp32 or both fp64; 1 <= f <= 64.  `info`: a device int32 tile of one element, zeroed by the caller and
-    shared by as many calls as the caller likes; it receives 1 + the lowest failing row of the first call in which a
-    system is not positive definite (that row of the result is NaN).  Without one the outcome is not reported.  The
-    call counts as one launch when m > 0 and as none otherwise, and never waits for the device."""
-    ratings, factors = self._as_device(ratings), self._as_device(factors)
-    dt = self.dtype_of(ratings)
-    for t in (ratings, factors):
-      _hip.refuse_not_float(self.dtype_of(t), 'als_solve')
-    if dt != self.dtype_of(factors):
-      raise TypeError('als_solve: operands of two dtypes (%s, %s); convert with astype first'
-                      % (dt, self.dtype_of(factors)))
-    if ratings.dim() != 2 or factors.dim() != 2 or ratings.shape[1] != factors.shape[0]:
-      raise ValueError('als_solve: shapes %s and %s do not fit' % (tuple(ratings.shape), tuple(factors.shape)))
-    m, f = int(ratings.shape[0]), int(factors.shape[1])
-    if not 1 <= f <= _hip.SP_ALS_MAX_F:
-      raise ValueError('als_solve: f = %d is outside 1 .. %d' % (f, _hip.SP_ALS_MAX_F))
-    out = self.empty((m, f), dt)
-    if m:
-      if info is None:
-        info = self.zeros((1,), np.int32)
-      before = self.launches
-      ratings, factors = self._knn_rows(ratings), self._knn_rows(factors)
-      self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
-      kernels.als_solve(ratings, factors, la, alpha, implicit, out, info)
-    return out
-
-  def fuzzy_step(self, points, centers, m, want_u=False, splits=0):
-    """One iteration of the reference's fuzzy k-means on a row tile as NEW tensors (labels int64 [n], sums [k, d],
-    wsum [k]), plus u [n, k] when `want_u` is set (sp_fuzzy_step: distances, memberships and the weighted sums fused;
-    without `want_u` nothing of size n x k is allocated or written).  With dist_ij = |x_i - c_j| (1e-10 where it is 0)
-    and p = dist ^ (1 / (m - 1)):  u_ij = p_ij / sum_j p_ij,  labels_i = the lowest j at the largest distance,
-    w = u ^ m,  sums = w^T . points,  wsum_j = sum_i w_ij.  Both operands fp32 or both fp64; m finite and > 1; k >= 1.
-    splits: into how many ranges the rows are cut (0: the library chooses); labels and u do not depend on it, bit for
-    bit.  The call counts as one launch and never waits for the device."""
-    points, centers = self._as_device(points), self._as_device(centers)
-    dt = self.dtype_of(points)
-    for t in (points, centers):
-      _hip.refuse_not_float(self.dtype_of(t), 'fuzzy_step')
-    if dt != self.dtype_of(centers):
-      raise TypeError('fuzzy_step: operands of two dtypes (%s, %s); convert with astype first'
-                      % (dt, self.dtype_of(centers)))
-    m = float(m)
-    if not (m > 1.0 and m != float('inf')):
-      raise ValueError('fuzzy_step: m = %r must be finite and > 1' % (m,))
-    if points.dim() != 2 or centers.dim() != 2 or points.shape[1] != centers.shape[1]:
-      raise ValueError('fuzzy_step: shapes %s and %s do not fit' % (tuple(points.shape), tuple(centers.shape)))
-    n, d = (int(v) for v in points.shape)
-    k = int(centers.shape[0])
-    if k < 1:
-      raise ValueError('fuzzy_step: k = %d must be at least 1' % k)
-    labels, sums, wsum = self.empty((n,), np.int64), self.empty((k, d), dt), self.empty((k,), dt)
-    u = self.empty((n, k), dt) if want_u else None
-    before = self.launches
-    points, centers = self._knn_rows(points), self._knn_rows(centers)
-    self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
-    kernels.fuzzy_step(points, centers, m, labels, sums, wsum, u=u, splits=splits)
-    return (labels, sums, wsum, u) if want_u else (labels, sums, wsum)
-
-  def lda_step(self, x, n, alpha, eta, iters, want_delta=True, want_doc_topics=True, splits=0):
-    """The tile body of the reference's LDA (CVB0) on a tile of documents as NEW tensors (delta [k, V], doc_topics
-    [D, k]; None in the place of one that is not wanted): `x` [V, D] terms x documents, `n` [k, V] the whole topic /
-    term counts (sp_lda_step: the per-document loops fused, nothing of size V x D is allocated).  Per document gamma
-    starts at 1 / k and is renewed `iters` times from q_tj = x_j p_tj / sum_t p_tj with p_tj = (n_tj + eta)
-    (gamma_t + alpha) / (sum_j |n_tj| + eta V); doc_topics is the last gamma (a row of NaN for a document without a
-    term), delta the sum over the documents of the last iteration's q.  Both operands fp32 or both fp64; 1 <= k <= 128,
-    iters >= 1, alpha and eta finite and > 0.  splits: into how many ranges the documents are cut (0: the library
-    chooses); doc_topics does not depend on it, bit for bit.  The call counts as one launch and never waits for the
-    device."""
-    x, n = self._as_device(x), self._as_device(n)
-    dt = self.dtype_of(x)
-    for t in (x, n):
-      _hip.refuse_not_float(self.dtype_of(t), 'lda_step')
-    if dt != self.dtype_of(n):
-      raise TypeError('lda_step: operands of two dtypes (%s, %s); convert with astype first' % (dt, self.dtype_of(n)))
-    if x.dim() != 2 or n.dim() != 2 or x.shape[0] != n.shape[1]:
-      raise ValueError('lda_step: shapes %s and %s do not fit' % (tuple(x.shape), tuple(n.shape)))
-    v, d = (int(s) for s in x.shape)
-    k = int(n.shape[0])
-    kernels.check_lda_params(k, alpha, eta, iters)
-    delta = self.empty((k, v), dt) if want_delta else None
-    doc_topics = self.empty((d, k), dt) if want_doc_topics else None
-    before = self.launches
-    x, n = self._knn_rows(x), self._knn_rows(n)
-    self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
-    kernels.lda_step(x, n, alpha, eta, iters, delta=delta, doc_topics=doc_topics, splits=splits)
-    return delta, doc_topics
-
-  def nb_step(self, x, labels, label_size, splits=0):
-    """The tile body of the reference's naive Bayes fit on a row tile as NEW tensors (S [label_size, d], df int64 [d],
-    bad int64 [1]): `x` [m, d] documents x terms, `labels` int64 [m] or [m, 1] (sp_nb_step: normalisation and label
-    sums fused, nothing of size m x d is allocated).  With r_i = sqrt(sum_j x_ij^2 / d):  S_lj = the sum over the rows
-    with labels_i == l of x_ij / r_i, in row order;  df_j = the rows with x_ij > 0;  bad = 0, or 1 + the lowest row
-    whose label is outside 0 .. label_size - 1 (it is left out of S and kept in df).  A row of zeros makes its label's
-    row of S NaN.  `x` fp32 or fp64; 1 <= label_size <= 128.  splits: into how many ranges the rows are cut (0: the
-    library chooses); df and bad do not depend on it.  The call counts as one launch when m > 0 and as none otherwise
-    (the three results are then zeros), and never waits for the device."""
-    x, labels = self._as_device(x), self._as_device(labels)
-    dt = self.dtype_of(x)
-    m, d, label_size = _hip.check_nb_operands(dt, x.shape, self.dtype_of(labels), labels.shape, label_size)
-    if int(splits) < 0:
-      raise ValueError('nb_step: splits = %d' % splits)
-    if not m:
-      return self.zeros((label_size, d), dt), self.zeros((d,), np.int64), self.zeros((1,), np.int64)
-    s, df, bad = self.empty((label_size, d), dt), self.empty((d,), np.int64), self.empty((1,), np.int64)
-    before = self.launches
-    if labels.dim() == 2:
-      labels = labels[:, 0]
-    if m > 1 and labels.stride(0) != 1:      # (a column of a wider array: the kernel reads the labels side by side)
-      labels = self.contiguous(labels)
-    x = self._knn_rows(x)
-    self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
-    kernels.nb_step(x, labels, label_size, s, df, bad, splits=splits)
-    return s, df, bad
-
-  def nbody_accel(self, x, y, z, mass, r0, m, g=6.67384e-11, rmin=1.0, splits=0):
-    """(ax, ay, az) as NEW tensors [m], the rows of one [3, m] array: the accelerations of bodies r0 .. r0 + m - 1 of
-    `x`, `y`, `z`, `mass` [n] under the gravity of all n (sp_nbody_accel: every pair in registers, nothing of size
-    n x n is allocated):  a_x[j] = sum over i != j of (g mass_i) / max(r_ij, rmin)^3 * (x_i - x_j), y and z alike.  All
-    four fp32 or all fp64.  The bits of a[j] depend on body j, the n sources and (n, splits) alone, so a band of targets
-    computed alone gives the bits the whole gives.  splits: into how many ranges the sources are cut (0: the library
-    chooses from n).  A strided view is first made contiguous.  The library issues one kernel with one range and two
-    with more (the second adds the ranges' partial sums), and the call counts as that many launches -- none when
-    m = 0 -- and never waits for the device.  Refusals: _hip.check_nbody_operands'."""
-    operands = [self._as_device(t) for t in (x, y, z, mass)]
-    dt, n, r0, m, g, rmin, splits = _hip.check_nbody_operands([self.dtype_of(t) for t in operands],
-                                                             [t.shape for t in operands], r0, m, g, rmin, splits)
-    before = self.launches
-    out = self.empty((3, m), dt)
-    if m:
-      operands = [self.contiguous(t) for t in operands]
-      kernels.nbody_accel(*operands, r0, m, out[0], out[1], out[2], g, rmin, splits=splits)
-      blocks = -(-n // 64)       # (the library's choice of ranges, nbody_ranges of csrc/nbody.hip, to count its launches)
-      ranges = 1 if blocks <= 1 else min(splits, blocks) if splits else min(-(-1024 // blocks), blocks)
-      self.launches = before + (1 if ranges == 1 else 2)   # (a strided operand's copy belongs to the call)
-    return out[0], out[1], out[2]
-
-  def affinity_degree(self, x, y, metric='rbf', gamma=1.0):
-    """The degrees D_i = sum_j a(x_i, y_j) of the rows of `x` [m, d] against ALL rows of `y` [n, d] as a NEW tensor [m]
-    (sp_affinity_degree: the affinities stay in registers, nothing of size m x n is allocated).  metric: 'rbf'
-    (a = exp(-gamma d2)), 'euclidean' (sqrt(d2)) or 'manhattan' (sum_f |x_f - y_f|), the distance in the difference
-    form.  Both operands fp32 or both fp64.  The bits of D_i depend on row i of x and on y alone, so a band of rows
-    computed alone gives the bits the whole gives.  The library issues one kernel, or two when n > 448 (the columns
-    are then cut into ranges whose partial degrees a second kernel adds); the call counts as one launch when m > 0
-    and as none otherwise, and never waits for the device.  Refusals: kernels.affinity_degree's."""
-    x, y = self._as_device(x), self._as_device(y)
-    dt, m, _, _ = kernels.affinity_operands('affinity_degree', x, y)
-    deg = self.empty((m,), dt)
-    if not m:
-      _hip.check_affinity_params(metric, gamma, 'affinity_degree')    # (with rows the launcher refuses)
-    else:
-      before = self.launches
-      kernels.affinity_degree(self._knn_rows(x), self._knn_rows(y), metric, gamma, deg)
-      self.launches = before + 1   # (the call counts as one: a strided operand's copy belongs to it)
-    return deg
-
-  def affinity_matrix(self, x, r0, y, metric='rbf', gamma=1.0, scale=None):
-    """The affinities of the rows of `x` [m, d] -- points r0 .. r0 + m - 1 of `y` [n, d] -- against all rows of `y` as a
-    NEW tensor [m, n] (sp_affinity_matrix, one workgroup per 64 x 64 tile, written exactly once).  Without `scale` the
-    plain a_ij; with `scale` [n] the normalised matrix of spectral clustering, a_ij * (scale[r0 + i] * scale[j]) with
-    exactly 1 at j = r0 + i -- symmetric bit for bit when the bands are put together.  Metrics and dtypes as
-    affinity_degree.  One kernel; the call counts as one launch when m > 0 and n > 0 and as none otherwise, and never
-    waits for the device.  Refusals: kernels.affinity_matrix's (they come before the launch and before it is
-    counted)."""
-    x, y = self._as_device(x), self._as_device(y)
-    scale = None if scale is None else self._as_device(scale)
-    dt, m, n, _ = kernels.affinity_operands('affinity_matrix', x, y, scale)
-    before = self.launches
-    out = self.empty((m, n), dt)
-    kernels.affinity_matrix(self._knn_rows(x), r0, self._knn_rows(y), metric, gamma, out,
-                            scale=None if scale is None else self.contiguous(scale))
-    self.launches = before + (1 if m and n else 0)   # (a strided operand's copy belongs to the call)
-    return out
 
   def convolve(self, image, filters):
     """stencil.py:29-45 as a GEMM: P[(n, x, y), (c, i, j)] = image[n, c, x+i, y+j] (0 beyond the edge) by one strided

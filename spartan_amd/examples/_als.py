@@ -3,10 +3,8 @@ host arrays otherwise -- the same normal equations, Cholesky and two triangular 
 the driver runnable on a backend of plain NumPy tiles."""
 import numpy as np
 
-from .. import context
+from .. import context, tile_checks
 from ..array import distarray
-
-MAX_F = 64       # SP_ALS_MAX_F of include/spartan_hip_als.h: the NumPy body refuses what the kernel refuses
 
 
 def _solve_rows(r, y, la, alpha, implicit):
@@ -59,15 +57,7 @@ def als_solve(ratings, factors, la, alpha, implicit, info=None):
   if fn is not None:
     return fn(ratings, factors, la, alpha, implicit=implicit, info=info)
   r, y = np.asarray(be.to_numpy(ratings)), np.asarray(be.to_numpy(factors))
-  for t in (r, y):
-    if t.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-      raise TypeError('als_solve: dtype %s is not supported (float32 float64); convert with astype first' % t.dtype)
-  if r.dtype != y.dtype:
-    raise TypeError('als_solve: operands of two dtypes (%s, %s); convert with astype first' % (r.dtype, y.dtype))
-  if r.ndim != 2 or y.ndim != 2 or r.shape[1] != y.shape[0]:
-    raise ValueError('als_solve: shapes %s and %s do not fit' % (r.shape, y.shape))
-  if not 1 <= y.shape[1] <= MAX_F:
-    raise ValueError('als_solve: f = %d is outside 1 .. %d' % (y.shape[1], MAX_F))
+  tile_checks.check_als_solve((r.dtype, y.dtype), (r.shape, y.shape))
   x, failed = _solve_rows(r, y, la, alpha, bool(implicit))
   if failed and info is not None and not info[0]:
     info[0] = failed

@@ -3,7 +3,7 @@ the backend has them (HipBackend: sp_potrf / sp_trsm_rlt / sp_syevj), LAPACK on 
 reference -- which keeps the drivers runnable on a backend of plain NumPy tiles."""
 import numpy as np
 
-from .. import context
+from .. import context, tile_checks
 from ..array import distarray
 
 
@@ -21,8 +21,7 @@ def potrf(t):
   if fn is not None:
     return fn(t)
   t = np.asarray(be.to_numpy(t))
-  if t.ndim != 2 or t.shape[0] != t.shape[1]:
-    raise ValueError('potrf: expected a square matrix, got shape %s' % (t.shape,))
+  tile_checks.check_potrf(t.dtype, t.shape)
   if t.shape[0] == 0:
     return t.copy()
   low, info = _lapack('potrf', t)(t, lower=1, clean=1)
@@ -40,6 +39,7 @@ def trsm_rlt(b, low):
   if fn is not None:
     return fn(b, low)
   b, low = np.asarray(be.to_numpy(b)), np.asarray(be.to_numpy(low))
+  tile_checks.check_trsm_rlt((b.dtype, low.dtype), (b.shape, low.shape))
   if b.size == 0:
     return b.copy()
   xt, info = _lapack('trtrs', low, b)(low, b.T, lower=1)
@@ -56,8 +56,7 @@ def syev(t):
   if fn is not None:
     return fn(t)
   t = np.asarray(be.to_numpy(t))
-  if t.ndim != 2 or t.shape[0] != t.shape[1]:
-    raise ValueError('syev: expected a square matrix, got shape %s' % (t.shape,))
+  tile_checks.check_syev(t.dtype, t.shape)
   if t.shape[0] == 0:
     return np.empty((0,), t.dtype), t.copy()
   w, v, info = _lapack('syevd', t)(t, lower=1)

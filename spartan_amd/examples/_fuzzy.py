@@ -3,17 +3,10 @@ NumPy on host arrays otherwise -- the same recipe in the tile's dtype (include/s
 driver runnable on a backend of plain NumPy tiles."""
 import numpy as np
 
-from .. import context
+from .. import context, tile_checks
 from ..array import distarray
 
-_FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
-
-
-def check_m(m, what='fuzzy_step'):
-  m = float(m)
-  if not (m > 1.0 and m != float('inf')):
-    raise ValueError('%s: m = %r must be finite and > 1' % (what, m))
-  return m
+check_m = tile_checks.check_fuzzy_m      # (the driver checks its own m with it)
 
 
 def step_numpy(x, c, m, want_u=False):
@@ -51,14 +44,5 @@ def fuzzy_step(points, centers, m, want_u=False):
   if fn is not None:
     return fn(points, centers, m, want_u=want_u)
   x, c = np.asarray(be.to_numpy(points)), np.asarray(be.to_numpy(centers))
-  for t in (x, c):
-    if t.dtype not in _FLOATS:
-      raise TypeError('fuzzy_step: dtype %s is not supported (float32 float64); convert with astype first' % t.dtype)
-  if x.dtype != c.dtype:
-    raise TypeError('fuzzy_step: operands of two dtypes (%s, %s); convert with astype first' % (x.dtype, c.dtype))
-  m = check_m(m)
-  if x.ndim != 2 or c.ndim != 2 or x.shape[1] != c.shape[1]:
-    raise ValueError('fuzzy_step: shapes %s and %s do not fit' % (x.shape, c.shape))
-  if c.shape[0] < 1:
-    raise ValueError('fuzzy_step: k = %d must be at least 1' % c.shape[0])
+  m = tile_checks.check_fuzzy_step((x.dtype, c.dtype), (x.shape, c.shape), m)[4]
   return step_numpy(x, c, m, want_u=want_u)

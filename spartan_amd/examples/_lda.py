@@ -3,25 +3,10 @@ arrays otherwise -- the same two-product form in the tile's dtype (include/spart
 runnable on a backend of plain NumPy tiles."""
 import numpy as np
 
-from .. import context
+from .. import context, tile_checks
 from ..array import distarray
 
-_FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
-MAX_K = 128
-
-
-def check_params(k, alpha, eta, iters, what='lda_step'):
-  """(k, alpha, eta, iters) as the kernel takes them, or ValueError for what it refuses."""
-  k, iters, alpha, eta = int(k), int(iters), float(alpha), float(eta)
-  if not 1 <= k <= MAX_K:
-    raise ValueError('%s: k = %d must be in 1 .. %d' % (what, k, MAX_K))
-  if iters < 1:
-    raise ValueError('%s: iters = %d must be at least 1' % (what, iters))
-  if not (alpha > 0.0 and alpha != float('inf')):
-    raise ValueError('%s: alpha = %r must be finite and > 0' % (what, alpha))
-  if not (eta > 0.0 and eta != float('inf')):
-    raise ValueError('%s: eta = %r must be finite and > 0' % (what, eta))
-  return k, alpha, eta, iters
+check_params = tile_checks.check_lda_params      # (the driver checks its own parameters with it)
 
 
 def step_numpy(x, n, alpha, eta, iters):
@@ -65,13 +50,6 @@ def lda_step(x, n, alpha, eta, iters, want_delta=True, want_doc_topics=True):
   if fn is not None:
     return fn(x, n, alpha, eta, iters, want_delta=want_delta, want_doc_topics=want_doc_topics)
   xh, nh = np.asarray(be.to_numpy(x)), np.asarray(be.to_numpy(n))
-  for t in (xh, nh):
-    if t.dtype not in _FLOATS:
-      raise TypeError('lda_step: dtype %s is not supported (float32 float64); convert with astype first' % t.dtype)
-  if xh.dtype != nh.dtype:
-    raise TypeError('lda_step: operands of two dtypes (%s, %s); convert with astype first' % (xh.dtype, nh.dtype))
-  if xh.ndim != 2 or nh.ndim != 2 or xh.shape[0] != nh.shape[1]:
-    raise ValueError('lda_step: shapes %s and %s do not fit' % (xh.shape, nh.shape))
-  k, alpha, eta, iters = check_params(nh.shape[0], alpha, eta, iters)
+  alpha, eta, iters = tile_checks.check_lda_step((xh.dtype, nh.dtype), (xh.shape, nh.shape), alpha, eta, iters)[4:7]
   delta, doc_topics = step_numpy(xh, nh, alpha, eta, iters)
   return (delta if want_delta else None, doc_topics if want_doc_topics else None)

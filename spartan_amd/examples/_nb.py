@@ -1,13 +1,13 @@
 """The tile body of the naive Bayes driver: backend.nb_step where the backend has it (HipBackend: sp_nb_step), NumPy on
 host arrays otherwise -- the same formulas, special values and `bad` in the tile's dtype (include/spartan_hip_nb.h),
 which keeps the driver runnable on a backend of plain NumPy tiles.  Both paths refuse through one function,
-_hip.check_nb_operands (the launcher and HipBackend.nb_step call it too)."""
+tile_checks.check_nb_operands (the launcher and HipBackend.nb_step call it too)."""
 import numpy as np
 
-from .. import _hip, context
+from .. import context, tile_checks
 from ..array import distarray
 
-check_operands = _hip.check_nb_operands
+check_operands = tile_checks.check_nb_operands
 
 
 def step_numpy(x, labels, label_size):
@@ -46,5 +46,5 @@ def nb_step(x, labels, label_size, splits=0):
   if fn is not None:
     return fn(x, labels, label_size, splits=splits)
   xn, ln = np.asarray(be.to_numpy(x)), np.asarray(be.to_numpy(labels))
-  _, _, label_size = check_operands(xn.dtype, xn.shape, ln.dtype, ln.shape, label_size)
+  _, _, label_size = check_operands(xn.dtype, xn.shape, ln.dtype, ln.shape, label_size, splits)
   return step_numpy(xn, ln, label_size)

@@ -1,13 +1,13 @@
 """The tile body of the n-body driver: backend.nbody_accel where the backend has it (HipBackend: sp_nbody_accel), NumPy
 on host arrays otherwise -- the same arithmetic per pair, operation for operation in the arrays' dtype
 (include/spartan_hip_nbody.h), which keeps the driver runnable on a backend of plain NumPy tiles.  Both paths refuse
-through one function, _hip.check_nbody_operands (the launcher and HipBackend.nbody_accel call it too)."""
+through one function, tile_checks.check_nbody_operands (the launcher and HipBackend.nbody_accel call it too)."""
 import numpy as np
 
-from .. import _hip, context
+from .. import context, tile_checks
 from ..array import distarray
 
-check_operands = _hip.check_nbody_operands
+check_operands = tile_checks.check_nbody_operands
 G = 6.67384e-11       # m^3 / (kg s^2): the reference's constant
 
 

@@ -3,17 +3,16 @@ them (HipBackend: sp_affinity_degree, sp_affinity_matrix), NumPy on host arrays 
 tile's dtype (include/spartan_hip_spectral.h), which keeps the driver runnable on a backend of plain NumPy tiles."""
 import numpy as np
 
-from .. import _hip, context
+from .. import _hip, context, tile_checks
 from ..array import distarray
 
-_FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
 METRICS = tuple(_hip.SP_AFF_METRICS)
 
 
 def check_params(metric, gamma, what='affinity'):
-  """gamma as a float, or what sp_affinity_* refuses (_hip.check_affinity_params: NotImplementedError for
+  """gamma as a float, or what sp_affinity_* refuses (tile_checks.check_affinity_params: NotImplementedError for
   'scaled_euclidean', ValueError for an unknown metric or a gamma that is not finite)."""
-  return _hip.check_affinity_params(metric, gamma, what)[1]
+  return tile_checks.check_affinity_params(metric, gamma, what)[1]
 
 
 def distance_numpy(x, y, metric):
@@ -59,18 +58,8 @@ def matrix_numpy(x, r0, y, metric, gamma, scale=None):
   return out
 
 
-def _host_operands(what, be, x, y, scale=None):
-  xh, yh = np.asarray(be.to_numpy(x)), np.asarray(be.to_numpy(y))
-  sh = None if scale is None else np.asarray(be.to_numpy(scale))
-  for t in (xh, yh, sh):
-    if t is not None and t.dtype not in _FLOATS:
-      raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, t.dtype))
-  for t in (yh, sh):
-    if t is not None and t.dtype != xh.dtype:
-      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, xh.dtype, t.dtype))
-  if xh.ndim != 2 or yh.ndim != 2 or xh.shape[1] != yh.shape[1]:
-    raise ValueError('%s: shapes %s and %s do not fit' % (what, xh.shape, yh.shape))
-  return xh, yh, sh
+def _host_operands(be, *tiles):
+  return [np.asarray(be.to_numpy(t)) for t in tiles if t is not None]
 
 
 def affinity_degree(x, y, metric='rbf', gamma=1.0):
@@ -82,8 +71,9 @@ def affinity_degree(x, y, metric='rbf', gamma=1.0):
   fn = getattr(be, 'affinity_degree', None)
   if fn is not None:
     return fn(x, y, metric, gamma)
-  xh, yh, _ = _host_operands('affinity_degree', be, x, y)
-  return degree_numpy(xh, yh, metric, check_params(metric, gamma, 'affinity_degree'))
+  xh, yh = _host_operands(be, x, y)
+  gamma = tile_checks.check_affinity_degree((xh.dtype, yh.dtype), (xh.shape, yh.shape), metric, gamma)[5]
+  return degree_numpy(xh, yh, metric, gamma)
 
 
 def affinity_matrix(x, r0, y, metric='rbf', gamma=1.0, scale=None):
@@ -95,11 +85,6 @@ def affinity_matrix(x, r0, y, metric='rbf', gamma=1.0, scale=None):
   fn = getattr(be, 'affinity_matrix', None)
   if fn is not None:
     return fn(x, r0, y, metric, gamma, scale=scale)
-  xh, yh, sh = _host_operands('affinity_matrix', be, x, y, scale)
-  gamma = check_params(metric, gamma, 'affinity_matrix')
-  r0 = int(r0)
-  if r0 < 0 or r0 + xh.shape[0] > yh.shape[0]:
-    raise ValueError('affinity_matrix: rows %d .. %d are not among the %d points' % (r0, r0 + xh.shape[0], yh.shape[0]))
-  if sh is not None and sh.shape != (yh.shape[0],):
-    raise ValueError('affinity_matrix: a scale of shape %s for %d points' % (sh.shape, yh.shape[0]))
-  return matrix_numpy(xh, r0, yh, metric, gamma, sh)
+  host = _host_operands(be, x, y, scale)
+  gamma, r0 = tile_checks.check_affinity_matrix([t.dtype for t in host], [t.shape for t in host], r0, metric, gamma)[5:]
+  return matrix_numpy(host[0], r0, host[1], metric, gamma, None if scale is None else host[2])

@@ -26,7 +26,7 @@ Deviations from the reference:
 """
 import numpy as np
 
-from .. import context, expr
+from .. import _hip, context, expr, tile_checks
 from ..array import distarray, extent
 from ..expr import base
 from . import _als
@@ -72,14 +72,10 @@ def als(A, la=0.065, alpha=40, implicit_feedback=False, num_features=20, num_ite
   float32), after num_iter iterations on the rating matrix `A` (expression / distributed array / NumPy array; 0 = not
   rated).  la: the regulariser; alpha: the confidence weight of implicit feedback; M: the starting item factors
   (default: the reference's rand with the average rating in column 0).  See the module docstring for the deviations."""
-  dtype = np.dtype(dtype)
-  if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-    raise TypeError('als: dtype %s is not supported (float32 float64)' % dtype)
+  dtype = tile_checks.check_float_dtype(dtype, 'als')
   if not la > 0:
     raise ValueError('als: la = %r must be positive (the solve is a Cholesky factorisation)' % (la,))
-  num_features = int(num_features)
-  if not 1 <= num_features <= _als.MAX_F:
-    raise ValueError('als: num_features = %d is outside 1 .. %d' % (num_features, _als.MAX_F))
+  num_features = tile_checks.check_count('als: num_features', num_features, _hip.SP_ALS_MAX_F)
   if num_iter < 1:
     raise ValueError('als: num_iter = %d' % num_iter)
   if isinstance(A, np.ndarray):

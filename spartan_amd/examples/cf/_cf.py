@@ -1,14 +1,17 @@
 """The tile bodies of the item recommender: backend.item_topk / backend.item_topk_merge where the backend has them
 (HipBackend: sp_item_topk / sp_item_topk_merge), NumPy on host arrays otherwise -- the same arithmetic in the same order
 (include/spartan_hip_cf.h), which keeps the driver runnable on a backend of plain NumPy tiles.  Both paths refuse
-through one function, _hip.check_item_topk_operands (the launcher and HipBackend.item_topk call it too)."""
+through one function, tile_checks.check_item_topk_operands (the launcher and HipBackend.item_topk call it too)."""
+import functools
+
 import numpy as np
 
-from ... import _hip, context
+from ... import context, tile_checks
 from ...array import distarray
+from .._select import select
 
-check_operands = _hip.check_item_topk_operands
-_NO_INDEX = np.iinfo(np.int64).max
+check_operands = tile_checks.check_item_topk_operands
+_select = functools.partial(select, largest=True)
 
 
 def similarities_numpy(targets, tnorm, sources, snorm):
@@ -23,22 +26,6 @@ def similarities_numpy(targets, tnorm, sources, snorm):
     sim = np.nan_to_num(dot / (tnorm[:, None] * snorm[None, :]))
   assert sim.dtype == dt
   return sim
-
-
-def _select(sim, idx, valid, k):
-  """Per row the k best of the candidates by (sim descending, idx ascending) among the valid ones, padded with
-  -inf / -1."""
-  m, cands = sim.shape
-  sim = np.where(valid, sim, -np.inf).astype(sim.dtype, copy=False)
-  idx = np.where(valid, idx, _NO_INDEX)
-  if cands < k:
-    sim = np.concatenate([sim, np.full((m, k - cands), -np.inf, sim.dtype)], axis=1)
-    idx = np.concatenate([idx, np.full((m, k - cands), _NO_INDEX, np.int64)], axis=1)
-  order = np.lexsort((idx, -sim), axis=1)[:, :k]
-  out_s = np.take_along_axis(sim, order, axis=1)
-  out_i = np.take_along_axis(idx, order, axis=1)
-  out_i[out_i == _NO_INDEX] = -1
-  return np.ascontiguousarray(out_s), np.ascontiguousarray(out_i)
 
 
 def item_topk_numpy(targets, tnorm, sources, snorm, k, index_offset=0):
@@ -81,7 +68,6 @@ def item_topk_merge(cand_sim, cand_idx, k):
   fn = getattr(be, 'item_topk_merge', None)
   if fn is not None:
     return fn(cand_sim, cand_idx, k)
-  sim, idx = np.asarray(be.to_numpy(cand_sim)), np.asarray(be.to_numpy(cand_idx)).astype(np.int64, copy=False)
-  if not 1 <= int(k) <= _hip.CF_MAX_K:
-    raise ValueError('item_topk_merge: k = %d is outside 1 .. %d' % (int(k), _hip.CF_MAX_K))
-  return _select(sim, idx, (idx >= 0) & ~np.isnan(sim), int(k))
+  sim, idx = np.asarray(be.to_numpy(cand_sim)), np.asarray(be.to_numpy(cand_idx))
+  k = tile_checks.check_item_topk_merge((sim.dtype, idx.dtype), (sim.shape, idx.shape), k)[3]
+  return _select(sim, idx, (idx >= 0) & ~np.isnan(sim), k)

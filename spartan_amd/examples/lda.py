@@ -29,7 +29,7 @@ max_iter_per_doc < 1, alpha or eta that is not finite and > 0 (with either not >
 term" fails silently), max_iter < 0 and a matrix that is not 2-D."""
 import numpy as np
 
-from .. import context, expr
+from .. import context, expr, tile_checks
 from ..array import distarray, extent
 from . import _lda
 
@@ -80,9 +80,7 @@ def learn_topics(terms_docs_matrix, k_topics, alpha=0.1, eta=0.1, max_iter=10, m
   if dtype is None:
     own = np.dtype(terms_docs_matrix.dtype)
     dtype = own if own in _FLOATS else np.dtype(np.float64)
-  dtype = np.dtype(dtype)
-  if dtype not in _FLOATS:
-    raise TypeError('learn_topics: dtype %s is not supported (float32 float64)' % dtype)
+  dtype = tile_checks.check_float_dtype(dtype, 'learn_topics')
   if topic_term_counts is None:
     topic_term_counts = expr.rand(k_topics, num_terms)
   elif isinstance(topic_term_counts, np.ndarray):

@@ -26,7 +26,7 @@ outside 0 .. label_size - 1 raises IndexError naming the row (NumPy would wrap a
 `predict_labels` is an addition."""
 import numpy as np
 
-from .. import _hip, context, expr
+from .. import _hip, context, expr, tile_checks
 from ..array import distarray, extent
 from . import _nb
 
@@ -59,9 +59,7 @@ def fit(data, labels, label_size, alpha=1.0, dtype=None):
   ((n,) or (n, 1), integers in 0 .. label_size - 1): {'scores_per_label_and_feature': (label_size, d),
   'scores_per_label': (label_size,)}, evaluated distributed arrays in `dtype` (default: the data's if it is float32 or
   float64, float64 otherwise).  See the module docstring for the formulas, the special values and the errors."""
-  alpha = float(alpha)
-  if not (alpha > 0.0 and alpha != float('inf')):
-    raise ValueError('fit: alpha = %r must be finite and > 0' % (alpha,))
+  alpha = tile_checks.check_finite_positive('fit: alpha', alpha)
   label_size = int(label_size)
   if not 1 <= label_size <= _hip.SP_NB_MAX_LABELS:
     raise ValueError('fit: label_size = %d must be in 1 .. %d' % (label_size, _hip.SP_NB_MAX_LABELS))
@@ -79,9 +77,7 @@ def fit(data, labels, label_size, alpha=1.0, dtype=None):
     raise TypeError('fit: labels of dtype %s; the labels are integers' % np.dtype(labels.dtype))
   if dtype is None:
     dtype = np.dtype(data.dtype) if np.dtype(data.dtype) in _FLOATS else np.dtype(np.float64)
-  dtype = np.dtype(dtype)
-  if dtype not in _FLOATS:
-    raise TypeError('fit: dtype %s is not supported (float32 float64)' % dtype)
+  dtype = tile_checks.check_float_dtype(dtype, 'fit')
   if np.dtype(labels.dtype) != np.int64:
     labels = expr.evaluate(expr.astype(labels, np.int64))
 

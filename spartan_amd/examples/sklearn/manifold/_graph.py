@@ -3,15 +3,7 @@ sp_graph_from_knn / sp_apsp), NumPy on host arrays otherwise -- the same arithme
 rounded add, wins only if it is smaller), which keeps the driver runnable on a backend of plain NumPy tiles."""
 import numpy as np
 
-from .... import context
-
-_FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
-
-
-def _refuse_not_float(dt, what):
-  if np.dtype(dt) not in _FLOATS:
-    raise TypeError('dtype %s is not supported by %s (supported: float32 float64); convert with astype first'
-                    % (np.dtype(dt), what))
+from .... import context, tile_checks
 
 
 def graph_from_knn(dist, idx):
@@ -27,12 +19,7 @@ def graph_from_knn(dist, idx):
 
 def graph_from_knn_numpy(dist, idx):
   """graph_from_knn on host arrays."""
-  _refuse_not_float(dist.dtype, 'graph_from_knn')
-  if idx.dtype != np.int64:
-    raise TypeError('graph_from_knn: indices of dtype %s (int64 expected); convert with astype first' % (idx.dtype,))
-  if dist.ndim != 2 or dist.shape != idx.shape:
-    raise ValueError('graph_from_knn: shapes %s and %s do not fit' % (dist.shape, idx.shape))
-  n = dist.shape[0]
+  _, n, _ = tile_checks.check_graph_from_knn((dist.dtype, idx.dtype), (dist.shape, idx.shape))
   w = np.full((n, n), np.inf, dist.dtype)
   np.fill_diagonal(w, 0)
   rows = np.broadcast_to(np.arange(n, dtype=np.int64)[:, None], idx.shape)
@@ -56,10 +43,7 @@ def apsp(w):
 def apsp_numpy(w):
   """apsp on a host array (which is not written)."""
   d = np.array(w)
-  _refuse_not_float(d.dtype, 'apsp')
-  if d.ndim != 2 or d.shape[0] != d.shape[1]:
-    raise ValueError('apsp: expected a square matrix, got shape %s' % (d.shape,))
-  n = d.shape[0]
+  _, n = tile_checks.check_apsp(d.dtype, d.shape)
   off = ~np.eye(n, dtype=bool)
   if np.any(~(d[off] >= 0)):
     raise ValueError('apsp: negative or NaN edge length')

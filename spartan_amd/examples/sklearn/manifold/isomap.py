@@ -27,7 +27,7 @@ alone goes far beyond them -- fit(X, embed=False) stops after it.
 """
 import numpy as np
 
-from .... import context
+from .... import context, tile_checks
 from ... import _dense
 from ..neighbors import NearestNeighbors
 from . import _graph
@@ -70,9 +70,7 @@ class Isomap(object):
       raise NotImplementedError("eigen_solver='arpack': there is no iterative eigensolver here; use 'dense'")
     if self.eigen_solver not in ('auto', 'dense'):
       raise ValueError('unknown eigen_solver %r' % (self.eigen_solver,))
-    k = int(self.n_neighbors)
-    if not 1 <= k <= MAX_NEIGHBORS:
-      raise ValueError('n_neighbors = %d is outside 1 .. %d' % (k, MAX_NEIGHBORS))
+    k = tile_checks.check_count('n_neighbors', self.n_neighbors, MAX_NEIGHBORS)
     be = context.get().backend
     dist, ind = self._neighbour_lists(X)
     graph = _graph.graph_from_knn(dist, ind)

@@ -3,25 +3,9 @@
 keeps the driver runnable on a backend of plain NumPy tiles."""
 import numpy as np
 
-from .... import context
+from .... import context, tile_checks
 from ....array import distarray
-
-_NO_INDEX = np.iinfo(np.int64).max
-
-
-def _select(d2, idx, valid, k):
-  """Per row the k smallest of the candidates by (d2, idx) among the valid ones, padded with +inf / -1."""
-  nq, m = d2.shape
-  d2 = np.where(valid, d2, np.inf).astype(d2.dtype, copy=False)
-  idx = np.where(valid, idx, _NO_INDEX)
-  if m < k:
-    d2 = np.concatenate([d2, np.full((nq, k - m), np.inf, d2.dtype)], axis=1)
-    idx = np.concatenate([idx, np.full((nq, k - m), _NO_INDEX, np.int64)], axis=1)
-  order = np.lexsort((idx, d2), axis=1)[:, :k]
-  out_d = np.take_along_axis(d2, order, axis=1)
-  out_i = np.take_along_axis(idx, order, axis=1)
-  out_i[out_i == _NO_INDEX] = -1
-  return np.ascontiguousarray(out_d), np.ascontiguousarray(out_i)
+from ..._select import select
 
 
 def _absent_pair(nq, k, dtype):
@@ -39,17 +23,14 @@ def knn(queries, points, k, index_offset=0):
   if fn is not None:
     return fn(queries, points, k, index_offset=index_offset)
   q, x = np.asarray(be.to_numpy(queries)), np.asarray(be.to_numpy(points))
-  if q.dtype != x.dtype:
-    raise TypeError('knn: operands of two dtypes (%s, %s); convert with astype first' % (q.dtype, x.dtype))
-  if q.ndim != 2 or x.ndim != 2 or q.shape[1] != x.shape[1]:
-    raise ValueError('knn: shapes %s and %s do not fit' % (q.shape, x.shape))
+  k = tile_checks.check_knn((q.dtype, x.dtype), (q.shape, x.shape), k)[4]
   d2 = np.zeros((q.shape[0], x.shape[0]), q.dtype)
   with np.errstate(all='ignore'):
     for j in range(q.shape[1]):            # (one feature after the other onto one accumulator, as the kernel adds them)
       diff = q[:, j, None] - x[None, :, j]
       d2 = d2 + diff * diff
   idx = np.broadcast_to(np.arange(x.shape[0], dtype=np.int64) + int(index_offset), d2.shape)
-  return _select(d2, idx, ~np.isnan(d2), int(k))
+  return select(d2, idx, ~np.isnan(d2), k)
 
 
 def knn_merge(cand_dist2, cand_idx, k):
@@ -61,5 +42,6 @@ def knn_merge(cand_dist2, cand_idx, k):
   fn = getattr(be, 'knn_merge', None)
   if fn is not None:
     return fn(cand_dist2, cand_idx, k)
-  d2, idx = np.asarray(be.to_numpy(cand_dist2)), np.asarray(be.to_numpy(cand_idx)).astype(np.int64, copy=False)
-  return _select(d2, idx, (idx >= 0) & ~np.isnan(d2), int(k))
+  d2, idx = np.asarray(be.to_numpy(cand_dist2)), np.asarray(be.to_numpy(cand_idx))
+  k = tile_checks.check_knn_merge((d2.dtype, idx.dtype), (d2.shape, idx.shape), k)[3]
+  return select(d2, idx, (idx >= 0) & ~np.isnan(d2), k)

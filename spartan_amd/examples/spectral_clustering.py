@@ -31,7 +31,7 @@ reference's default the last tile's partial sums replace the others', and the ou
 depends on the arbitrary sign numpy.linalg.eig gives the Ritz vectors, which decides the starting rows)."""
 import numpy as np
 
-from .. import context, expr
+from .. import context, expr, tile_checks
 from ..array import distarray, extent
 from . import _spectral, lanczos
 from .sklearn.cluster.k_means_ import KMeans
@@ -81,9 +81,7 @@ def _prepare(points, metric, gamma, dtype, what):
   if dtype is None:
     own = np.dtype(points.dtype)
     dtype = own if own in _FLOATS else np.dtype(np.float64)
-  dtype = np.dtype(dtype)
-  if dtype not in _FLOATS:
-    raise TypeError('%s: dtype %s is not supported (float32 float64)' % (what, dtype))
+  dtype = tile_checks.check_float_dtype(dtype, what)
   host = np.ascontiguousarray(np.asarray(points.glom()), dtype=dtype)
   return points, host, gamma, dtype
 

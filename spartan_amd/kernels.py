@@ -10,7 +10,7 @@ import inspect
 
 import numpy as np
 
-from . import _hip, devarray
+from . import _hip, devarray, tile_checks
 from ._hip import check
 from .devarray import Event  # noqa: F401  (bench.py / tools time launches with it)
 
@@ -68,17 +68,9 @@ def _writes(*names):
   return deco
 
 
-def _float_dtype(what, first, *others):
-  """The dtype of `first` for a launcher `what` that exists in float32 and float64 only: TypeError for an operand of
-  another dtype, or for one of `others` (None is skipped) whose dtype is not that of `first`, in the operands' order."""
-  dt = np_dtype_of(first)
-  for t in (first,) + others:
-    if t is None:
-      continue
-    _hip.refuse_not_float(np_dtype_of(t), what)
-    if np_dtype_of(t) != dt:
-      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, dt, np_dtype_of(t)))
-  return dt
+def _dtypes(*tensors):
+  """The dtypes of the operands of a launcher, in their order, for its tile_checks function (None is skipped)."""
+  return [np_dtype_of(t) for t in tensors if t is not None]
 
 
 class Workspace(object):
@@ -469,9 +461,8 @@ def potrf(a, info):
   its Cholesky factor L, the strict upper triangle zero (sp_potrf); `info`, a device int32, receives 0 or the order
   of the first leading minor that is not positive definite.  Nothing waits for the device."""
   _require_device(a, info)
-  dt = _float_dtype('potrf', a)
-  assert a.dim() == 2 and a.shape[0] == a.shape[1] and np_dtype_of(info) == np.int32
-  n = int(a.shape[0])
+  dt, n = tile_checks.check_potrf(np_dtype_of(a), a.shape)
+  assert np_dtype_of(info) == np.int32
   assert n <= 1 or a.stride(1) == 1
   lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
   code = _hip.sp_dtype(dt)
@@ -485,11 +476,7 @@ def trsm_rlt(b, l):
   """In place: b <- x with x . l^T = b, `l` square lower triangular (its upper triangle is not read), `b` [m, n]; both
   fp32 or both fp64, views with inner stride 1 (sp_trsm_rlt)."""
   _require_device(b, l)
-  dt = _float_dtype('trsm_rlt', b)
-  _float_dtype('trsm_rlt', l)
-  assert dt == np_dtype_of(l) and b.dim() == 2 and l.dim() == 2
-  m, n = (int(v) for v in b.shape)
-  assert tuple(l.shape) == (n, n), (b.shape, l.shape)
+  dt, m, n = tile_checks.check_trsm_rlt(_dtypes(b, l), (b.shape, l.shape))
   assert n <= 1 or (b.stride(1) == 1 and l.stride(1) == 1)
   if m and n:
     check(_hip.extras().sp_trsm_rlt(_hip.sp_dtype(dt), _p(l), _ld(l), n, _p(b), _ld(b), m, _stream()))
@@ -504,9 +491,8 @@ def syevj(a, w, v, info):
   converge.  Returns the number of sweeps.  The call waits for the device once per sweep (a word that says whether
   the off-diagonal norm is below n u ||a||_F) and for nothing else."""
   _require_device(a, w, v, info)
-  dt = _float_dtype('syevj', a)
-  assert a.dim() == 2 and a.shape[0] == a.shape[1] and np_dtype_of(info) == np.int32
-  n = int(a.shape[0])
+  dt, n = tile_checks.check_syev(np_dtype_of(a), a.shape, 'syevj')
+  assert np_dtype_of(info) == np.int32
   assert np_dtype_of(w) == dt and np_dtype_of(v) == dt and tuple(w.shape) == (n,) and tuple(v.shape) == (n, n)
   assert n <= 1 or (a.stride(1) == 1 and v.stride(1) == 1 and w.stride(0) == 1)
   lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
@@ -525,19 +511,14 @@ def knn(q, x, k, dist2, idx, index_offset=0, splits=0):
   (sp_knn).  q, x: both fp32 or both fp64, views with inner stride 1; dist2 (their dtype) and idx (int64): contiguous
   [nq, k].  splits: 0 = the library chooses into how many ranges the points are cut, s >= 1 = min(s, np) ranges."""
   _require_device(q, x, dist2, idx)
-  dt = _float_dtype('knn', q)
-  _float_dtype('knn', x)
-  assert dt == np_dtype_of(x) == np_dtype_of(dist2) and np_dtype_of(idx) == np.int64
-  assert q.dim() == 2 and x.dim() == 2 and q.shape[1] == x.shape[1], (q.shape, x.shape)
-  nq, d = (int(v) for v in q.shape)
-  n = int(x.shape[0])
-  k = int(k)
+  dt, nq, n, d, k, splits = tile_checks.check_knn(_dtypes(q, x), (q.shape, x.shape), k, splits)
+  assert np_dtype_of(dist2) == dt and np_dtype_of(idx) == np.int64
   assert tuple(dist2.shape) == (nq, k) and tuple(idx.shape) == (nq, k) and dist2.is_contiguous() and idx.is_contiguous()
   lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
   code = _hip.sp_dtype(dt)
-  need = lib.sp_knn_workspace_bytes(code, nq, n, d, k, int(splits))
+  need = lib.sp_knn_workspace_bytes(code, nq, n, d, k, splits)
   ws = _ws.get(need, q.device) if need else None
-  check(lib.sp_knn(code, _p(q), _ld(q), nq, _p(x), _ld(x), n, d, k, int(index_offset), int(splits), _p(dist2), _p(idx),
+  check(lib.sp_knn(code, _p(q), _ld(q), nq, _p(x), _ld(x), n, d, k, int(index_offset), splits, _p(dist2), _p(idx),
                    _p(ws), ws.numel() if need else 0, _stream()))
   return dist2, idx
 
@@ -548,11 +529,8 @@ def knn_merge(cand_dist2, cand_idx, k, dist2, idx):
   index are padding (sp_knn_merge).  cand_dist2 (fp32 / fp64) and cand_idx (int64): [nq, m] views with inner stride 1
   and ONE row stride; dist2, idx: contiguous [nq, k]."""
   _require_device(cand_dist2, cand_idx, dist2, idx)
-  dt = _float_dtype('knn_merge', cand_dist2)
-  assert np_dtype_of(cand_idx) == np.int64 and np_dtype_of(idx) == np.int64 and np_dtype_of(dist2) == dt
-  assert cand_dist2.dim() == 2 and tuple(cand_dist2.shape) == tuple(cand_idx.shape)
-  nq, m = (int(v) for v in cand_dist2.shape)
-  k = int(k)
+  dt, nq, m, k = tile_checks.check_knn_merge(_dtypes(cand_dist2, cand_idx), (cand_dist2.shape, cand_idx.shape), k)
+  assert np_dtype_of(idx) == np.int64 and np_dtype_of(dist2) == dt
   assert _ld(cand_dist2) == _ld(cand_idx), (cand_dist2.stride(), cand_idx.stride())
   assert tuple(dist2.shape) == (nq, k) and tuple(idx.shape) == (nq, k) and dist2.is_contiguous() and idx.is_contiguous()
   check(_hip.extras().sp_knn_merge(_hip.sp_dtype(dt), _p(cand_dist2), _p(cand_idx), _ld(cand_dist2), nq, m, k, _p(dist2),
@@ -568,10 +546,12 @@ def item_topk(targets, tnorm, sources, snorm, k, sim, idx, index_offset=0, split
   ascending order, / (tnorm[j] * snorm[i]), nan_to_num).  targets, sources: both fp32 or both fp64, views with inner
   stride 1 (two column ranges of one table will do); tnorm [m], snorm [ns] contiguous, of their dtype; sim (their
   dtype) and idx (int64): contiguous [m, k].  splits: 0 = the library chooses into how many ranges the sources are cut,
-  s >= 1 = min(s, ns) ranges.  Refusals: _hip.check_item_topk_operands', before any launch.  Owns the workspace."""
+  s >= 1 = min(s, ns) ranges.  Refusals: tile_checks.check_item_topk_operands', before any launch.  Owns the workspace.
+  Returns the number of kernels the library issues: 1, or 2 where it needs a workspace (more than one range, whose
+  candidates the second kernel merges)."""
   _require_device(targets, tnorm, sources, snorm, sim, idx)
-  dt, users, m, ns, k, splits = _hip.check_item_topk_operands(
-      [np_dtype_of(t) for t in (targets, tnorm, sources, snorm, sim)], targets.shape, tnorm.shape, sources.shape,
+  dt, users, m, ns, k, splits = tile_checks.check_item_topk_operands(
+      _dtypes(targets, tnorm, sources, snorm, sim), targets.shape, tnorm.shape, sources.shape,
       snorm.shape, k, splits)
   assert np_dtype_of(idx) == np.int64 and tnorm.is_contiguous() and snorm.is_contiguous()
   assert tuple(sim.shape) == (m, k) and tuple(idx.shape) == (m, k) and sim.is_contiguous() and idx.is_contiguous()
@@ -581,7 +561,7 @@ def item_topk(targets, tnorm, sources, snorm, k, sim, idx, index_offset=0, split
   ws = _ws.get(need, targets.device) if need else None
   check(lib.sp_item_topk(code, _p(targets), _ld(targets), _p(tnorm), m, _p(sources), _ld(sources), _p(snorm), ns, users,
                          k, int(index_offset), splits, _p(sim), _p(idx), _p(ws), ws.numel() if need else 0, _stream()))
-  return sim, idx
+  return 2 if need else 1
 
 
 @_writes('sim', 'idx')
@@ -590,11 +570,8 @@ def item_topk_merge(cand_sim, cand_idx, k, sim, idx):
   with a negative index are padding (sp_item_topk_merge).  cand_sim (fp32 / fp64) and cand_idx (int64): [m, cands]
   views with inner stride 1 and ONE row stride; sim, idx: contiguous [m, k]."""
   _require_device(cand_sim, cand_idx, sim, idx)
-  dt = _float_dtype('item_topk_merge', cand_sim)
-  assert np_dtype_of(cand_idx) == np.int64 and np_dtype_of(idx) == np.int64 and np_dtype_of(sim) == dt
-  assert cand_sim.dim() == 2 and tuple(cand_sim.shape) == tuple(cand_idx.shape)
-  m, cands = (int(v) for v in cand_sim.shape)
-  k = int(k)
+  dt, m, cands, k = tile_checks.check_item_topk_merge(_dtypes(cand_sim, cand_idx), (cand_sim.shape, cand_idx.shape), k)
+  assert np_dtype_of(idx) == np.int64 and np_dtype_of(sim) == dt
   assert _ld(cand_sim) == _ld(cand_idx), (cand_sim.stride(), cand_idx.stride())
   assert tuple(sim.shape) == (m, k) and tuple(idx.shape) == (m, k) and sim.is_contiguous() and idx.is_contiguous()
   check(_hip.extras().sp_item_topk_merge(_hip.sp_dtype(dt), _p(cand_sim), _p(cand_idx), _ld(cand_sim), m, cands, k,
@@ -609,9 +586,8 @@ def apsp(d, info):
   blocked Floyd-Warshall, a candidate d[i][k] + d[k][j] wins only if it is smaller).  `info`, a device int32, receives
   0, or 1 if an off-diagonal entry is NaN or negative (`d` is then unspecified).  Nothing waits for the device."""
   _require_device(d, info)
-  dt = _float_dtype('apsp', d)
-  assert d.dim() == 2 and d.shape[0] == d.shape[1] and np_dtype_of(info) == np.int32
-  n = int(d.shape[0])
+  dt, n = tile_checks.check_apsp(np_dtype_of(d), d.shape)
+  assert np_dtype_of(info) == np.int32
   assert n <= 1 or d.stride(1) == 1
   check(_hip.extras().sp_apsp(_hip.sp_dtype(dt), _p(d), _ld(d), n, _p(info), _stream()))
   return d
@@ -624,10 +600,8 @@ def graph_from_knn(dist, idx, w):
   smallest weight stated for it in either direction, on both sides; idx < 0 is padding (sp_graph_from_knn).  `w`: of
   dist's dtype, a view with inner stride 1."""
   _require_device(dist, idx, w)
-  dt = _float_dtype('graph_from_knn', dist)
-  assert np_dtype_of(idx) == np.int64 and np_dtype_of(w) == dt
-  assert dist.dim() == 2 and tuple(dist.shape) == tuple(idx.shape)
-  n, k = (int(v) for v in dist.shape)
+  dt, n, k = tile_checks.check_graph_from_knn(_dtypes(dist, idx), (dist.shape, idx.shape))
+  assert np_dtype_of(w) == dt
   assert tuple(w.shape) == (n, n) and (n <= 1 or w.stride(1) == 1)
   assert k <= 1 or (dist.stride(1) == 1 and idx.stride(1) == 1)
   assert n <= 1 or _ld(dist) == _ld(idx), (dist.stride(), idx.stride())
@@ -643,13 +617,7 @@ def als_solve(r, y, la, alpha, implicit, x, info):
   receives 1 + the lowest row whose system is not positive definite if it is still 0; that row of x is NaN.  TypeError
   for other dtypes, ValueError for shapes that do not fit or f outside 1 .. 64.  Nothing waits for the device."""
   _require_device(r, y, x, info)
-  dt = _float_dtype('als_solve', r, y)
-  if r.dim() != 2 or y.dim() != 2 or r.shape[1] != y.shape[0]:
-    raise ValueError('als_solve: shapes %s and %s do not fit' % (tuple(r.shape), tuple(y.shape)))
-  m, n = (int(v) for v in r.shape)
-  f = int(y.shape[1])
-  if not 1 <= f <= _hip.SP_ALS_MAX_F:
-    raise ValueError('als_solve: f = %d is outside 1 .. %d' % (f, _hip.SP_ALS_MAX_F))
+  dt, m, n, f = tile_checks.check_als_solve(_dtypes(r, y), (r.shape, y.shape))
   if tuple(x.shape) != (m, f) or np_dtype_of(x) != dt:
     raise ValueError('als_solve: a target of shape %s and dtype %s for %d rows and %d features of %s'
                      % (tuple(x.shape), np_dtype_of(x), m, f, dt))
@@ -674,18 +642,8 @@ def fuzzy_step(points, centers, m, labels, sums, wsum, u=None, splits=0):
   min(s, ceil(n / 64)) ranges.  TypeError for other or mixed dtypes, ValueError for m that is not finite and > 1,
   k < 1 or shapes that do not fit -- all before any launch.  Nothing waits for the device."""
   _require_device(points, centers, labels, sums, wsum, u)
-  dt = _float_dtype('fuzzy_step', points, centers, sums, wsum, u)
-  m = float(m)
-  if not (m > 1.0 and m != float('inf')):
-    raise ValueError('fuzzy_step: m = %r must be finite and > 1' % (m,))
-  if points.dim() != 2 or centers.dim() != 2 or points.shape[1] != centers.shape[1]:
-    raise ValueError('fuzzy_step: shapes %s and %s do not fit' % (tuple(points.shape), tuple(centers.shape)))
-  n, d = (int(v) for v in points.shape)
-  k = int(centers.shape[0])
-  if k < 1:
-    raise ValueError('fuzzy_step: k = %d must be at least 1' % k)
-  if int(splits) < 0:
-    raise ValueError('fuzzy_step: splits = %d' % splits)
+  dt, n, k, d, m, splits = tile_checks.check_fuzzy_step(_dtypes(points, centers, sums, wsum, u),
+                                                        (points.shape, centers.shape), m, splits)
   if tuple(sums.shape) != (k, d) or tuple(wsum.shape) != (k,) or (u is not None and tuple(u.shape) != (n, k)):
     raise ValueError('fuzzy_step: targets of shapes %s, %s, %s for %d rows, %d centres and %d features'
                      % (tuple(sums.shape), tuple(wsum.shape), None if u is None else tuple(u.shape), n, k, d))
@@ -694,24 +652,10 @@ def fuzzy_step(points, centers, m, labels, sums, wsum, u=None, splits=0):
   assert wsum.is_contiguous() and (labels is None or labels.is_contiguous())
   lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
   code = _hip.sp_dtype(dt)
-  ws = _ws.get(lib.sp_fuzzy_step_workspace_bytes(code, n, k, d, int(splits)), points.device)
-  check(lib.sp_fuzzy_step(code, _p(points), _ld(points), n, _p(centers), _ld(centers), k, d, m, int(splits), _p(labels),
+  ws = _ws.get(lib.sp_fuzzy_step_workspace_bytes(code, n, k, d, splits), points.device)
+  check(lib.sp_fuzzy_step(code, _p(points), _ld(points), n, _p(centers), _ld(centers), k, d, m, splits, _p(labels),
                           _p(sums), _ld(sums), _p(wsum), _p(u), k if u is None else _ld(u), _p(ws), ws.numel(), _stream()))
   return labels, sums, wsum, u
-
-
-def check_lda_params(k, alpha, eta, iters, what='lda_step'):
-  """(alpha, eta, iters) as the library takes them, or ValueError for what sp_lda_step refuses."""
-  alpha, eta = float(alpha), float(eta)
-  if not 1 <= int(k) <= _hip.SP_LDA_MAX_K:
-    raise ValueError('%s: k = %d must be in 1 .. %d' % (what, int(k), _hip.SP_LDA_MAX_K))
-  if int(iters) < 1:
-    raise ValueError('%s: iters = %d must be at least 1' % (what, int(iters)))
-  if not (alpha > 0.0 and alpha != float('inf')):
-    raise ValueError('%s: alpha = %r must be finite and > 0' % (what, alpha))
-  if not (eta > 0.0 and eta != float('inf')):
-    raise ValueError('%s: eta = %r must be finite and > 0' % (what, eta))
-  return alpha, eta, int(iters)
 
 
 @_writes('delta', 'doc_topics')
@@ -724,22 +668,16 @@ def lda_step(x, n, alpha, eta, iters, delta=None, doc_topics=None, splits=0):
   for other or mixed dtypes, ValueError for k outside 1 .. 128, iters < 1, alpha or eta not finite and > 0 or shapes
   that do not fit -- all before any launch.  Nothing waits for the device."""
   _require_device(x, n, delta, doc_topics)
-  dt = _float_dtype('lda_step', x, n, delta, doc_topics)
-  if x.dim() != 2 or n.dim() != 2 or x.shape[0] != n.shape[1]:
-    raise ValueError('lda_step: shapes %s and %s do not fit' % (tuple(x.shape), tuple(n.shape)))
-  v, d = (int(s) for s in x.shape)
-  k = int(n.shape[0])
-  alpha, eta, iters = check_lda_params(k, alpha, eta, iters)
-  if int(splits) < 0:
-    raise ValueError('lda_step: splits = %d' % splits)
+  dt, v, d, k, alpha, eta, iters, splits = tile_checks.check_lda_step(_dtypes(x, n, delta, doc_topics), (x.shape, n.shape),
+                                                                      alpha, eta, iters, splits)
   if (delta is not None and tuple(delta.shape) != (k, v)) or (doc_topics is not None and tuple(doc_topics.shape) != (d, k)):
     raise ValueError('lda_step: targets of shapes %s, %s for %d terms, %d documents and %d topics'
                      % (None if delta is None else tuple(delta.shape),
                         None if doc_topics is None else tuple(doc_topics.shape), v, d, k))
   lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
   code = _hip.sp_dtype(dt)
-  ws = _ws.get(lib.sp_lda_step_workspace_bytes(code, v, d, k, iters, int(splits)), x.device)
-  check(lib.sp_lda_step(code, _p(x), _ld(x), v, d, _p(n), _ld(n), k, alpha, eta, iters, int(splits), _p(delta),
+  ws = _ws.get(lib.sp_lda_step_workspace_bytes(code, v, d, k, iters, splits), x.device)
+  check(lib.sp_lda_step(code, _p(x), _ld(x), v, d, _p(n), _ld(n), k, alpha, eta, iters, splits, _p(delta),
                         v if delta is None else _ld(delta), _p(doc_topics), k if doc_topics is None else _ld(doc_topics),
                         _p(ws), ws.numel(), _stream()))
   return delta, doc_topics
@@ -756,10 +694,9 @@ def nb_step(x, labels, label_size, out_s, out_df, out_bad, splits=0):
   min(s, ceil(m / 64)) ranges.  TypeError for other dtypes, ValueError for label_size outside 1 .. 128 or shapes that
   do not fit -- all before any launch.  Nothing waits for the device."""
   _require_device(x, labels, out_s, out_df, out_bad)
-  dt = _float_dtype('nb_step', x, out_s)
-  m, d, label_size = _hip.check_nb_operands(dt, x.shape, np_dtype_of(labels), labels.shape, label_size)
-  if int(splits) < 0:
-    raise ValueError('nb_step: splits = %d' % splits)
+  dt = np_dtype_of(x)
+  m, d, label_size = tile_checks.check_nb_operands(dt, x.shape, np_dtype_of(labels), labels.shape, label_size, splits)
+  tile_checks.one_float_dtype('nb_step', (dt, np_dtype_of(out_s)))
   if tuple(out_s.shape) != (label_size, d) or tuple(out_df.shape) != (d,) or tuple(out_bad.shape) != (1,):
     raise ValueError('nb_step: targets of shapes %s, %s, %s for %d labels and %d features'
                      % (tuple(out_s.shape), tuple(out_df.shape), tuple(out_bad.shape), label_size, d))
@@ -784,11 +721,12 @@ def nbody_accel(x, y, z, mass, r0, m, ax, ay, az, g, rmin, splits=0):
   library chooses from n into how many ranges the sources are cut, s >= 1 = min(s, ceil(n / 64)) ranges.  TypeError for
   other or mixed dtypes, ValueError for shapes that do not fit, targets that are not among the bodies, splits < 0, a g
   that is not finite or an rmin that is not finite and > 0 -- all before any launch.  Owns the workspace.  Nothing
-  waits for the device."""
+  waits for the device.  Returns the number of kernels the library issues: 1, or 2 where it needs a workspace (more than
+  one range, whose partial sums the second kernel adds)."""
   _require_device(x, y, z, mass, ax, ay, az)
   operands = (x, y, z, mass, ax, ay, az)
-  dt, n, r0, m, g, rmin, splits = _hip.check_nbody_operands([np_dtype_of(t) for t in operands],
-                                                           [t.shape for t in operands[:4]], r0, m, g, rmin, splits)
+  dt, n, r0, m, g, rmin, splits = tile_checks.check_nbody_operands(_dtypes(*operands), [t.shape for t in operands[:4]],
+                                                                   r0, m, g, rmin, splits)
   if any(tuple(t.shape) != (m,) for t in (ax, ay, az)):
     raise ValueError('nbody_accel: targets of shapes %s for %d bodies' % ([tuple(t.shape) for t in (ax, ay, az)], m))
   assert all(t.is_contiguous() for t in operands), [t.stride() for t in operands]
@@ -798,15 +736,7 @@ def nbody_accel(x, y, z, mass, r0, m, ax, ay, az, g, rmin, splits=0):
   ws = _ws.get(need, x.device) if need else None
   check(lib.sp_nbody_accel(code, g, rmin, _p(x), _p(y), _p(z), _p(mass), n, r0, m, _p(ax), _p(ay), _p(az), splits, _p(ws),
                            ws.numel() if need else 0, _stream()))
-  return ax, ay, az
-
-
-def affinity_operands(what, x, y, *others):
-  """(dtype, m, n, d) of the operands of an affinity launcher, or its TypeError / ValueError."""
-  dt = _float_dtype(what, x, y, *others)
-  if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
-    raise ValueError('%s: shapes %s and %s do not fit' % (what, tuple(x.shape), tuple(y.shape)))
-  return dt, int(x.shape[0]), int(y.shape[0]), int(x.shape[1])
+  return 2 if need else 1
 
 
 @_writes('deg')
@@ -818,8 +748,7 @@ def affinity_degree(x, y, metric, gamma, deg):
   shapes that do not fit, NotImplementedError for 'scaled_euclidean' -- all before any launch.  Nothing waits for the
   device."""
   _require_device(x, y, deg)
-  dt, m, n, d = affinity_operands('affinity_degree', x, y, deg)
-  code_m, gamma = _hip.check_affinity_params(metric, gamma, 'affinity_degree')
+  dt, m, n, d, code_m, gamma = tile_checks.check_affinity_degree(_dtypes(x, y, deg), (x.shape, y.shape), metric, gamma)
   if tuple(deg.shape) != (m,):
     raise ValueError('affinity_degree: a target of shape %s for %d rows' % (tuple(deg.shape), m))
   assert deg.is_contiguous()
@@ -839,13 +768,8 @@ def affinity_matrix(x, r0, y, metric, gamma, out, scale=None):
   include/spartan_hip_spectral.h).  Operands all fp32 or all fp64, views with inner stride 1; out [m, n] the same.
   Refusals as affinity_degree's, and ValueError for r0 < 0 or r0 + m > n.  Nothing waits for the device."""
   _require_device(x, y, out, scale)
-  dt, m, n, d = affinity_operands('affinity_matrix', x, y, out, scale)
-  code_m, gamma = _hip.check_affinity_params(metric, gamma, 'affinity_matrix')
-  r0 = int(r0)
-  if r0 < 0 or r0 + m > n:
-    raise ValueError('affinity_matrix: rows %d .. %d are not among the %d points' % (r0, r0 + m, n))
-  if scale is not None and tuple(scale.shape) != (n,):
-    raise ValueError('affinity_matrix: a scale of shape %s for %d points' % (tuple(scale.shape), n))
+  dt, m, n, d, code_m, gamma, r0 = tile_checks.check_affinity_matrix(
+      _dtypes(x, y, scale, out), [t.shape for t in (x, y, scale) if t is not None], r0, metric, gamma)
   if tuple(out.shape) != (m, n):
     raise ValueError('affinity_matrix: a target of shape %s for %d rows and %d points' % (tuple(out.shape), m, n))
   assert (n <= 1 or out.stride(1) == 1) and (scale is None or scale.is_contiguous())

@@ -10,7 +10,7 @@ import re
 import numpy as np
 import pytest
 
-from spartan_amd import _hip
+from spartan_amd import _hip, tile_checks
 from spartan_amd.examples.cf import _cf
 from tests import cf_cases as cc
 
@@ -139,7 +139,7 @@ def test_workspace_sizes():
 
 def test_operand_refusals():
   f32, f64 = np.dtype(np.float32), np.dtype(np.float64)
-  check = _hip.check_item_topk_operands
+  check = tile_checks.check_item_topk_operands
   assert check([f64] * 4, (7, 3), (3,), (7, 9), (9,), 5) == (f64, 7, 3, 9, 5, 0)
   assert check([f32] * 4, (0, 3), (3,), (0, 0), (0,), 128, 4) == (f32, 0, 3, 0, 128, 4)
   for bad in (np.int32, np.float16, np.complex128, object):

@@ -96,7 +96,7 @@ def test_the_oracle_is_the_reference_loop():
 
 def test_check_params_refuses_what_the_kernel_refuses():
   from spartan_amd.examples import _lda
-  assert _lda.check_params(5, 0.1, 0.2, 3) == (5, 0.1, 0.2, 3) and _lda.MAX_K == _hip.SP_LDA_MAX_K == 128
+  assert _lda.check_params(5, 0.1, 0.2, 3) == (5, 0.1, 0.2, 3) and _hip.SP_LDA_MAX_K == 128
   assert _lda.check_params(128, 1e-300, 1e300, 1)[0] == 128
   for k in (0, -1, 129):
     with pytest.raises(ValueError, match='k = '):

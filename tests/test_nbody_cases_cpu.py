@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from spartan_amd import _hip
+from spartan_amd import _hip, tile_checks
 from spartan_amd.examples import _nbody
 from tests import nbody_cases as nc
 
@@ -116,27 +116,27 @@ def test_the_header_declares_what_is_bound():
 def test_operand_refusals():
   f32, f64 = np.dtype(np.float32), np.dtype(np.float64)
   ok = ([f64] * 4, [(9,)] * 4, 0, 9, 1.0, 1.0)
-  assert _hip.check_nbody_operands(*ok)[:4] == (f64, 9, 0, 9)
+  assert tile_checks.check_nbody_operands(*ok)[:4] == (f64, 9, 0, 9)
   for bad in (np.int32, np.float16, np.complex128, object):
     with pytest.raises(TypeError, match='astype first'):
-      _hip.check_nbody_operands([f64, f64, np.dtype(bad), f64], [(9,)] * 4, 0, 9, 1.0, 1.0)
+      tile_checks.check_nbody_operands([f64, f64, np.dtype(bad), f64], [(9,)] * 4, 0, 9, 1.0, 1.0)
   with pytest.raises(TypeError, match='two dtypes.*astype first'):
-    _hip.check_nbody_operands([f64, f64, f32, f64], [(9,)] * 4, 0, 9, 1.0, 1.0)
+    tile_checks.check_nbody_operands([f64, f64, f32, f64], [(9,)] * 4, 0, 9, 1.0, 1.0)
   for shapes in ([(9,), (9,), (8,), (9,)], [(9, 1)] * 4, [(3, 3)] * 4):
     with pytest.raises(ValueError, match='1-D and of equal length'):
-      _hip.check_nbody_operands([f64] * 4, shapes, 0, 1, 1.0, 1.0)
+      tile_checks.check_nbody_operands([f64] * 4, shapes, 0, 1, 1.0, 1.0)
   for r0, m in ((-1, 2), (0, 10), (9, 1), (3, -1)):
     with pytest.raises(ValueError, match='not among'):
-      _hip.check_nbody_operands([f64] * 4, [(9,)] * 4, r0, m, 1.0, 1.0)
+      tile_checks.check_nbody_operands([f64] * 4, [(9,)] * 4, r0, m, 1.0, 1.0)
   with pytest.raises(ValueError, match='splits'):
-    _hip.check_nbody_operands([f64] * 4, [(9,)] * 4, 0, 9, 1.0, 1.0, splits=-1)
+    tile_checks.check_nbody_operands([f64] * 4, [(9,)] * 4, 0, 9, 1.0, 1.0, splits=-1)
   for g in (float('nan'), float('inf'), -float('inf')):
     with pytest.raises(ValueError, match='g = '):
-      _hip.check_nbody_operands([f64] * 4, [(9,)] * 4, 0, 9, g, 1.0)
+      tile_checks.check_nbody_operands([f64] * 4, [(9,)] * 4, 0, 9, g, 1.0)
   with pytest.raises(ValueError, match='g = '):
-    _hip.check_nbody_operands([f32] * 4, [(9,)] * 4, 0, 9, 1e300, 1.0)         # not finite in float32
+    tile_checks.check_nbody_operands([f32] * 4, [(9,)] * 4, 0, 9, 1e300, 1.0)         # not finite in float32
   for rmin in (0.0, -1.0, float('nan'), float('inf')):
     with pytest.raises(ValueError, match='rmin'):
-      _hip.check_nbody_operands([f64] * 4, [(9,)] * 4, 0, 9, 1.0, rmin)
+      tile_checks.check_nbody_operands([f64] * 4, [(9,)] * 4, 0, 9, 1.0, rmin)
   with pytest.raises(ValueError, match='rmin'):
-    _hip.check_nbody_operands([f32] * 4, [(9,)] * 4, 0, 9, 1.0, 1e-60)         # 0 in float32
+    tile_checks.check_nbody_operands([f32] * 4, [(9,)] * 4, 0, 9, 1.0, 1e-60)         # 0 in float32
