@@ -22,6 +22,7 @@ from . import devarray as D
 from . import sparse as sparse_mod
 from .array import distarray, tile
 from .backend_hip_extras import ExtrasTileBodies
+from .backend_hip_svm import SvmTileBodies
 from .expr.local import LocalMapLocationExpr, FnCallExpr, LocalInput
 from .program import ProgramTooLarge, class_of, join_class
 
@@ -391,7 +392,7 @@ def _no_copy(t):
   raise lower.NotLowerable('an operand the kernels cannot address in place')
 
 
-class HipBackend(ExtrasTileBodies):
+class HipBackend(ExtrasTileBodies, SvmTileBodies):
   name = 'hip'
 
   def __init__(self, device=None):

@@ -17,5 +17,8 @@ frequencies fused) per row band of the documents, `predict` / `predict_labels` s
 `nbody.move` / `simulate` (all-pairs gravity) runs one sp_nbody_accel (every pair in registers, nothing of size n x n)
 per band of bodies and updates velocities and positions on the map kernels;
 `cf.ItemBasedRecommender` (item-based collaborative filtering) runs one sp_item_topk (cosine similarity and top-k fused,
-nothing of size N x N) per column band and source step of the rating table and merges the steps with sp_item_topk_merge.
+nothing of size N x N) per column band and source step of the rating table and merges the steps with sp_item_topk_merge;
+`disdca_svm.fit` / `predict` (the linear SVM by distributed dual coordinate ascent) runs one sp_svm_dca (a band's whole
+loop over its rows, w on chip) per row band and iteration and forms w with the reference's expression on the map and
+reduce kernels.
 Like `sort` they are imported on first use, not with the package."""

@@ -739,6 +739,37 @@ def nbody_accel(x, y, z, mass, r0, m, ax, ay, az, g, rmin, splits=0):
   return 2 if need else 1
 
 
+def _side_by_side(t, n):
+  """Whether the n elements of `t` -- [n] or an [n, 1] view -- lie next to each other in memory."""
+  return int(t.numel()) == n and (n <= 1 or t.stride(0) == 1)
+
+
+@_writes('alpha_out', 'w_out')
+def svm_dca(x, y, alpha, w0, scaled_lambda, chains, alpha_out, w_out=None):
+  """One pass of the reference's dual coordinate ascent over the rows of a tile (sp_svm_dca;
+  include/spartan_hip_svm.h states the arithmetic of a row and the order of its two inner products): `x` [m, d] fp32 or
+  fp64, a view with inner stride 1; `y`, `alpha` ([m] or [m, 1]) and `w0` ([d] or [d, 1]) of its dtype, each with its
+  elements next to each other.  The rows are cut into `chains` consecutive bands; every band starts from w = w0 and
+  walks its rows in order.  alpha_out ([m] or [m, 1], elements next to each other; it may be `alpha` itself) <- the
+  new dual variables, w_out ([chains, d] contiguous, or None) <- the w every chain ends with.  TypeError for other or
+  mixed dtypes, ValueError for d outside 1 .. 4096, chains < 1, a scaled_lambda that is not finite and > 0 or shapes
+  that do not fit -- all before any launch.  One kernel, no workspace.  Nothing waits for the device."""
+  _require_device(x, y, alpha, w0, alpha_out, w_out)
+  dt, m, d, scaled_lambda, chains = tile_checks.check_svm_dca(
+      _dtypes(x, y, alpha, w0, alpha_out, w_out)[:4], (x.shape, y.shape, alpha.shape, w0.shape), scaled_lambda, chains)
+  tile_checks.one_float_dtype('svm_dca', _dtypes(x, alpha_out, w_out))
+  if tuple(alpha_out.shape) not in ((m,), (m, 1)) or (w_out is not None and tuple(w_out.shape) != (chains, d)):
+    raise ValueError('svm_dca: targets of shapes %s, %s for %d rows, %d chains and %d features'
+                     % (tuple(alpha_out.shape), None if w_out is None else tuple(w_out.shape), m, chains, d))
+  assert all(_side_by_side(t, m) for t in (y, alpha, alpha_out)) and _side_by_side(w0, d), \
+      [t.stride() for t in (y, alpha, alpha_out, w0)]
+  assert w_out is None or w_out.is_contiguous()
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  check(lib.sp_svm_dca(_hip.sp_dtype(dt), _p(x), _ld(x), m, d, _p(y), _p(alpha), _p(w0), scaled_lambda, chains,
+                       _p(alpha_out), _p(w_out), _stream()))
+  return alpha_out, w_out
+
+
 @_writes('deg')
 def affinity_degree(x, y, metric, gamma, deg):
   """deg[i] <- sum_j a(x_i, y_j) over all rows of `y` (sp_affinity_degree; include/spartan_hip_spectral.h states the

@@ -342,3 +342,39 @@ def check_item_topk_operands(dtypes, t_shape, tnorm_shape, s_shape, snorm_shape,
   if splits < 0:
     raise ValueError('%s: splits = %d is negative' % (what, splits))
   return dtypes[0], t_shape[0], t_shape[1], s_shape[1], k, splits
+
+
+def check_svm_dca(dtypes, shapes, scaled_lambda, chains=1, what='svm_dca'):
+  """(dtype, m, d, scaled_lambda, chains) of a dual coordinate ascent pass on x [m, d], y, alpha and w0 -- `dtypes` and
+  `shapes` are theirs, in that order -- or what sp_svm_dca refuses: TypeError ("astype first") for arrays that are not
+  float32 / float64 or that are of two dtypes; ValueError for an x that is not 2-D, a y or alpha that is not [m] or
+  [m, 1], a w0 that is not [d] or [d, 1], a d outside 1 .. SP_SVM_MAX_D, chains < 1 and a scaled_lambda that is not
+  finite and > 0 in the arrays' dtype.  The one copy: the launcher, the backend, the NumPy body of examples/_svm.py and
+  the driver all refuse through it."""
+  dtypes = [np.dtype(d) for d in dtypes]
+  for d in dtypes:
+    if d not in _hip.FLOATS:
+      raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, d))
+  for d in dtypes[1:]:
+    if d != dtypes[0]:
+      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, dtypes[0], d))
+  x, y, alpha, w0 = (tuple(int(v) for v in s) for s in shapes)
+  if len(x) != 2:
+    raise ValueError('%s: expected data of shape (m, d), got %s' % (what, x))
+  m, d = x
+  for name, shape in (('y', y), ('alpha', alpha)):
+    if shape not in ((m,), (m, 1)):
+      raise ValueError('%s: %s of shape %s for %d rows' % (what, name, shape, m))
+  if not 1 <= d <= _hip.SP_SVM_MAX_D:
+    raise ValueError('%s: d = %d must be in 1 .. %d' % (what, d, _hip.SP_SVM_MAX_D))
+  if w0 not in ((d,), (d, 1)):
+    raise ValueError('%s: w0 of shape %s for %d features' % (what, w0, d))
+  chains = int(chains)
+  if chains < 1:
+    raise ValueError('%s: chains = %d must be at least 1' % (what, chains))
+  scaled_lambda = float(scaled_lambda)
+  with np.errstate(all='ignore'):
+    st = dtypes[0].type(scaled_lambda)
+  if not (st > 0 and np.isfinite(st)):
+    raise ValueError('%s: scaled_lambda = %r must be finite and > 0 in %s' % (what, scaled_lambda, dtypes[0]))
+  return dtypes[0], m, d, scaled_lambda, chains
