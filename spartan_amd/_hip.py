@@ -340,6 +340,13 @@ _EXTRAS_ABI = {
     'spartan_hip_svm.h': {
         'sp_svm_dca': (C.c_int, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _f64, _i64, _vp, _vp, _vp]),
     },
+    'spartan_hip_mf.h': {
+        'sp_sgd_mf_plan_bytes': (_sz, [_i64, _i64, _i64]),
+        'sp_sgd_mf_plan': (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _sz]),
+        'sp_sgd_mf_host': (C.c_int, [_i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _vp]),
+        'sp_sgd_mf': (C.c_int, [_i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp,
+                                C.POINTER(C.c_int64), _vp]),
+    },
 }
 EXPORTS_EXTRAS = list(_EXTRAS_ABI['spartan_hip_extras.h'])
 EXPORTS_EIG = list(_EXTRAS_ABI['spartan_hip_eig.h'])
@@ -353,12 +360,15 @@ EXPORTS_NB = list(_EXTRAS_ABI['spartan_hip_nb.h'])
 EXPORTS_NBODY = list(_EXTRAS_ABI['spartan_hip_nbody.h'])
 EXPORTS_CF = list(_EXTRAS_ABI['spartan_hip_cf.h'])
 EXPORTS_SVM = list(_EXTRAS_ABI['spartan_hip_svm.h'])
+EXPORTS_MF = list(_EXTRAS_ABI['spartan_hip_mf.h'])
 KNN_MAX_K = 128       # SP_KNN_MAX_K of spartan_hip_knn.h
 CF_MAX_K = 128        # SP_CF_MAX_K of spartan_hip_cf.h (tests/test_cf_cases_cpu.py keeps the two equal)
 SP_ALS_MAX_F = 64     # of spartan_hip_als.h
 SP_LDA_MAX_K = 128    # of spartan_hip_lda.h
 SP_NB_MAX_LABELS = 128   # of spartan_hip_nb.h
 SP_SVM_MAX_D = 4096      # of spartan_hip_svm.h
+SP_MF_MAX_F = 512        # of spartan_hip_mf.h
+SP_MF_WIDE = 64          # of spartan_hip_mf.h (tests/test_netflix_cases_cpu.py keeps header, binding and plans equal)
 SP_AFF_METRICS = {'rbf': 0, 'euclidean': 1, 'manhattan': 2}   # SP_AFF_* of spartan_hip_spectral.h
 
 
@@ -368,7 +378,7 @@ _extras = None
 def extras():
   """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn / knn_merge, apsp / graph_from_knn,
   als_solve, fuzzy_step, lda_step, affinity_degree / affinity_matrix, nb_step, nbody_accel, item_topk / item_topk_merge,
-  svm_dca);
+  svm_dca, sgd_mf / sgd_mf_plan / sgd_mf_host);
   raises if it has not been built.  What their Python side refuses: tile_checks.py."""
   global _extras
   if _extras is None:

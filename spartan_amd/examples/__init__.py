@@ -20,5 +20,8 @@ per band of bodies and updates velocities and positions on the map kernels;
 nothing of size N x N) per column band and source step of the rating table and merges the steps with sp_item_topk_merge;
 `disdca_svm.fit` / `predict` (the linear SVM by distributed dual coordinate ascent) runs one sp_svm_dca (a band's whole
 loop over its rows, w on chip) per row band and iteration and forms w with the reference's expression on the map and
-reduce kernels.
+reduce kernels;
+`netflix.sgd` (stochastic-gradient matrix factorisation of a sparse rating matrix) runs one sp_sgd_mf (a block's
+sequential loop over its ratings, level-scheduled, with the loop's bits) per block of a stratum and updates the factors
+in place through select / update_slice.
 Like `sort` they are imported on first use, not with the package."""

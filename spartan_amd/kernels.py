@@ -770,6 +770,87 @@ def svm_dca(x, y, alpha, w0, scaled_lambda, chains, alpha_out, w_out=None):
   return alpha_out, w_out
 
 
+def sgd_mf_plan(m, n, indptr, indices):
+  """The level schedule of a tile of ratings [m, n] in canonical CSR (sp_sgd_mf_plan; include/spartan_hip_mf.h states
+  its layout) from HOST arrays `indptr` [m + 1] and `indices` [nnz]: a uint8 array of the bytes in use.  Host code: no
+  device is needed.  HipError for what the library refuses (nnz >= 2^31, an indptr that is not monotone from 0 to nnz, an
+  index outside 0 .. n - 1)."""
+  indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+  indices = np.ascontiguousarray(indices, dtype=np.int32)
+  m, n, nnz = int(m), int(n), int(indices.shape[0])
+  if indptr.shape != (m + 1,):
+    raise ValueError('sgd_mf_plan: indptr of shape %s for %d rows' % (indptr.shape, m))
+  lib = _hip.extras()
+  need = int(lib.sp_sgd_mf_plan_bytes(m, n, nnz))
+  if need == 0:
+    raise _hip.HipError('sp_sgd_mf_plan: bad sizes m=%d n=%d nnz=%d (each below 2^31)' % (m, n, nnz))
+  buf = np.empty((need + 7) // 8, np.int64)               # (8-byte aligned)
+  check(lib.sp_sgd_mf_plan(m, n, nnz, indptr.ctypes.data, indices.ctypes.data if nnz else None, buf.ctypes.data, need))
+  return buf.view(np.uint8)[:int(buf[6])].copy()
+
+
+def sgd_mf_plan_parts(plan):
+  """The arrays of a plan (a uint8 host array as sgd_mf_plan returns it) as views: {'m', 'n', 'nnz', 'levels', 'wide',
+  'entry', 'row', 'col' [nnz], 'level_off' [levels + 1], 'segments' [segments, 4] of (kind, first level, last level + 1,
+  0); kind 1 is a wide level, 0 a run of narrow ones}."""
+  head = plan[:128].view(np.int64)
+  m, n, nnz, levels, segs = (int(v) for v in head[1:6])
+  i32 = lambda off, count: plan[int(off):int(off) + 4 * count].view(np.int32)   # noqa: E731
+  return {'m': m, 'n': n, 'nnz': nnz, 'levels': levels, 'wide': int(head[12]), 'entry': i32(head[7], nnz),
+          'row': i32(head[8], nnz), 'col': i32(head[9], nnz), 'level_off': i32(head[10], levels + 1),
+          'segments': i32(head[11], 4 * segs).reshape(segs, 4)}
+
+
+def sgd_mf_host(shape, indptr, indices, vals, u, m, lr=None, abs_err=None, order=None):
+  """The SGD sequence of include/spartan_hip_mf.h as the library's plain host loop (sp_sgd_mf_host) on NumPy arrays:
+  the tile `shape` with `indptr`, `indices`, `vals`; `u` [rows, f] and `m` [cols, f] (C-contiguous rows, of vals' dtype)
+  are updated IN PLACE; `abs_err` [nnz] (or None) <- |d| per entry; `order` (int32 [nnz], or None for tile order) is the
+  order in which the entries are taken.  Refusals: tile_checks.check_sgd_mf's, then the library's."""
+  dt, rows, cols, f, lr = tile_checks.check_sgd_mf([vals.dtype, u.dtype, m.dtype], shape, u.shape, m.shape, lr)
+  indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+  indices = np.ascontiguousarray(indices, dtype=np.int32)
+  vals = np.ascontiguousarray(vals)
+  nnz = int(indices.shape[0])
+  assert indptr.shape == (rows + 1,) and vals.shape == (nnz,), (indptr.shape, vals.shape)
+  for t in (u, m):
+    assert t.strides[1] == t.itemsize and t.strides[0] % t.itemsize == 0 and t.flags.writeable, t.strides
+  if abs_err is not None:
+    assert abs_err.dtype == dt and abs_err.shape == (nnz,) and abs_err.flags.c_contiguous
+  if order is not None:
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    assert order.shape == (nnz,)
+  ld = lambda t: max(t.strides[0] // t.itemsize, f) if t.shape[0] > 1 else f   # noqa: E731
+  ptr = lambda t: None if t is None or t.size == 0 else t.ctypes.data          # noqa: E731
+  check(_hip.extras().sp_sgd_mf_host(_hip.sp_dtype(dt), rows, cols, f, nnz, indptr.ctypes.data, ptr(indices), ptr(vals),
+                                     ptr(u), ld(u), ptr(m), ld(m), lr, ptr(abs_err), ptr(order)))
+
+
+@_writes('u', 'm', 'abs_err')
+def sgd_mf(shape, vals, plan_dev, plan_host, u, m, lr=None, abs_err=None):
+  """One SGD pass over a tile of ratings of `shape` whose values are `vals` [nnz] (sp_sgd_mf; include/spartan_hip_mf.h
+  states the sequence and the order of its dot): `u` [rows, f] and `m` [cols, f], fp32 or fp64 like `vals`, views with
+  inner stride 1, are updated IN PLACE with the bits of the sequential loop; `plan_host` is sgd_mf_plan's array for
+  the tile's structure and `plan_dev` its copy in HBM; `abs_err` ([nnz] contiguous, or None) <- |d| per entry.  Returns
+  the number of kernels launched (one per segment of the plan; 0 for an empty tile).  TypeError for other or mixed
+  dtypes, ValueError for shapes that do not fit, f outside 1 .. 512 and an lr that is not finite -- all before any
+  launch.  Nothing waits for the device."""
+  _require_device(vals, plan_dev, u, m, abs_err)
+  dt, rows, cols, f, lr = tile_checks.check_sgd_mf(_dtypes(vals, u, m), shape, u.shape, m.shape, lr)
+  nnz = int(vals.numel())
+  if abs_err is not None:
+    tile_checks.one_float_dtype('sgd_mf', _dtypes(vals, abs_err))
+    if tuple(abs_err.shape) != (nnz,):
+      raise ValueError('sgd_mf: abs_err of shape %s for %d ratings' % (tuple(abs_err.shape), nnz))
+    assert abs_err.is_contiguous()
+  assert nnz <= 1 or vals.stride(0) == 1
+  if nnz == 0:
+    return 0
+  launched = C.c_int64(0)
+  check(_hip.extras().sp_sgd_mf(_hip.sp_dtype(dt), rows, cols, f, nnz, _p(vals), _p(plan_dev), plan_host.ctypes.data, _p(u),
+                                _ld(u), _p(m), _ld(m), lr, _p(abs_err), C.byref(launched), _stream()))
+  return int(launched.value)
+
+
 @_writes('deg')
 def affinity_degree(x, y, metric, gamma, deg):
   """deg[i] <- sum_j a(x_i, y_j) over all rows of `y` (sp_affinity_degree; include/spartan_hip_spectral.h states the

@@ -58,7 +58,7 @@ def _cat(parts):
 
 class CsrTile(object):
   """Device blob of a sparse tile."""
-  __slots__ = ('shape', 'dtype', 'indptr', 'indices', 'data', '_plan', '_block_plan', '_transposed')
+  __slots__ = ('shape', 'dtype', 'indptr', 'indices', 'data', '_plan', '_block_plan', '_mf_plan', '_transposed')
   is_sparse_tile = True
 
   def __init__(self, shape, dtype, indptr, indices, data):
@@ -69,6 +69,7 @@ class CsrTile(object):
     self.data = data
     self._plan = None      # sp_csr_spmv_plan output, made on the first matrix x vector product and kept
     self._block_plan = None   # spmv_block_plan's: the column-blocked copy of the entries, or False (none for this tile)
+    self._mf_plan = None      # sgd_mf_plan's: (host bytes, their copy in HBM) of the SGD level schedule, made on first use
     self._transposed = None   # the transposed tile, made on first use and kept (tiles are immutable)
 
   @property
@@ -113,6 +114,16 @@ def spmv_block_plan(t):
       if int(plan[:8].numpy().view(np.int64)[0]) == 1:      # (0: a row not sorted by column)
         t._block_plan = plan
   return t._block_plan
+
+
+def sgd_mf_plan(t):
+  """(host uint8 array, its copy in HBM) of the level schedule of the tile's entries (include/spartan_hip_mf.h;
+  kernels.sgd_mf_plan builds it on the host): an analysis of the STRUCTURE, so one device-to-host copy of indptr and
+  indices on the tile's first SGD pass; later epochs and other ranks of factors reuse it."""
+  if t._mf_plan is None:
+    host = kernels.sgd_mf_plan(t.shape[0], t.shape[1], t.indptr.numpy(), t.indices.numpy())
+    t._mf_plan = (host, D.from_numpy(host))
+  return t._mf_plan
 
 
 def _check_dtype(dtype):

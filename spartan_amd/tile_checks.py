@@ -378,3 +378,36 @@ def check_svm_dca(dtypes, shapes, scaled_lambda, chains=1, what='svm_dca'):
   if not (st > 0 and np.isfinite(st)):
     raise ValueError('%s: scaled_lambda = %r must be finite and > 0 in %s' % (what, scaled_lambda, dtypes[0]))
   return dtypes[0], m, d, scaled_lambda, chains
+
+
+def check_sgd_mf(dtypes, tile_shape, u_shape, m_shape, lr=None, what='sgd_mf'):
+  """(dtype, m, n, f, lr) of one SGD pass over a tile of ratings [m, n] with the factors U [m, f] and M [n, f] --
+  `dtypes` are those of the tile's values, of U and of M -- or what sp_sgd_mf refuses: TypeError ("astype first") for
+  arrays that are not float32 / float64 or that are of two dtypes; ValueError for a tile that is not 2-D, a U that is
+  not [m, f], an M that is not [n, f], an f outside 1 .. SP_MF_MAX_F and an lr that is not finite in the arrays' dtype.
+  lr = None is the reference's float32(1e-5).  The one copy: the launcher, the backend, the NumPy body of
+  examples/_netflix.py and the driver all refuse through it."""
+  dtypes = [np.dtype(d) for d in dtypes]
+  for d in dtypes:
+    if d not in _hip.FLOATS:
+      raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, d))
+  for d in dtypes[1:]:
+    if d != dtypes[0]:
+      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, dtypes[0], d))
+  v, u, mm = (tuple(int(s) for s in shape) for shape in (tile_shape, u_shape, m_shape))
+  if len(v) != 2:
+    raise ValueError('%s: expected ratings of shape (m, n), got %s' % (what, v))
+  m, n = v
+  if len(u) != 2 or u[0] != m:
+    raise ValueError('%s: U of shape %s for %d rows of ratings' % (what, u, m))
+  f = u[1]
+  if not 1 <= f <= _hip.SP_MF_MAX_F:
+    raise ValueError('%s: rank f = %d must be in 1 .. %d' % (what, f, _hip.SP_MF_MAX_F))
+  if mm != (n, f):
+    raise ValueError('%s: M of shape %s for %d columns of ratings and rank %d' % (what, mm, n, f))
+  lr = float(np.float32(1e-5)) if lr is None else float(lr)
+  with np.errstate(all='ignore'):
+    lt = dtypes[0].type(lr)
+  if not np.isfinite(lt):
+    raise ValueError('%s: lr = %r must be finite in %s' % (what, lr, dtypes[0]))
+  return dtypes[0], m, n, f, lr
