@@ -1,5 +1,6 @@
 // Split tier of sp_gemm_ws (fp32): the contraction on the bf16 matrix pipe, which on gfx950 runs at 16 x the rate of
-// the fp32 one (v_mfma_f32_32x32x16_bf16: 16 k per 32 cycles; v_mfma_f32_32x32x2_f32: 2 per 64).  Included by gemm.hip.
+// the fp32 one (v_mfma_f32_16x16x32_bf16: 32 k of a 16 x 16 block per 16 cycles; v_mfma_f32_32x32x2_f32: 2 k of a
+// 32 x 32 block per 64).  Included by gemm.hip.
 //
 // THE CUT.  Every fp32 operand is cut into three bf16 numbers, v = hi + mid + lo with hi = bf16(v), mid = bf16(v - hi),
 // lo = bf16((v - hi) - mid), all conversions round-to-nearest-even.  bf16 keeps 8 significant bits, so for v in
@@ -21,8 +22,13 @@
 //   * the terms left out:                                        <= 2.004 u S
 //   * the accumulation of the 6 K exact products in fp32:        any order of adding n numbers with one rounding to
 //     nearest per addend errs by at most (n - 1) u sum|p| (1 + O(n u)); sum|p| <= (1 + 2^-8)^2 S, so <= 6.05 K u S.
-//     What the instruction does inside is not documented; measured (tools/mfma_bf16_probe.hip, see kmeans_split.hpp):
-//     at most 2.5 u (|c| + sum|p|) per MFMA of 16 products, i.e. 6 K / 16 MFMAs per element -> 0.94 K u (S + max|c|)
+//     The mainloop takes them two terms to an MFMA: 3 K / 16 v_mfma_f32_16x16x32_bf16 per element, each the sum of 32
+//     products and C, and one of the three mixes ah bh with am bm, 2^-16 of its size.  What the instruction does
+//     inside is not documented; measured (tools/mfma_bf16_probe.hip, its 16x16x32 part: 20 000 sums of 32 products
+//     whose halves differ by 2^-16 or not at all, C zero, small or a running sum of up to 2^7): it is neither the exact
+//     sum rounded once nor two 16-product steps rounded to nearest; with the smaller half in k 0..15, as here, it errs
+//     by at most 2.7 u (|c| + sum|p|) per MFMA -> 0.51 K u (S + max|c|) (3.0 u with the smaller half in k 16..31,
+//     and over the whole GEMM the rms error is 0.3 % larger that way round)
 //   * the epilogue's one rounding of C += (accumulate)           (as in the fp32 tier)
 // against the fp32 tier's k-ordered fmaf chain, K u S.  For uniform [-1, 1) data S ~ K / 4 and the errors add like a
 // random walk; measured ratios of the two tiers' max errors are in profiles/gemm_bf16_split_notes.md.
@@ -49,26 +55,37 @@
 // Shapes whose images would not fit under GS_IMAGE_CAP stay on the fp32 tier (cutting K into slabs that accumulate
 // into C is not built: 32768^3 would need seven).
 //
-// MAINLOOP (sp_gemm_glds_kernel_bf16x3).  256 x (64 WN) workgroup tile, 2 x WN waves of 128 x 64 each (the k-means
-// split kernel's geometry), k-tiles of 16 brought by global_load_lds_dwordx4 into two LDS stages; 18 ds_read_b128
-// fragment reads and 48 MFMAs per wave and k-step.  The loop is software-pipelined one k-tile ahead IN REGISTERS: the
-// MFMAs of k-tile t take every operand from VGPRs that were filled during k-tile t - 1, so no LDS latency stands
-// between the barrier and the first MFMA.  During k-tile t a wave
-//   * issues the 48 MFMAs of tile t (term order and (i, j) walk as ever: the bits of C do not depend on the pipeline);
-//   * reads the 18 fragments of tile t + 1 from stage (t + 1) & 1, one per MFMA gap: hi into a second register set
-//     (the hi fragments are live to the last term), lo and mid into the registers of tile t as the term order frees
-//     them (al after term 0, bl after 1, am after 3, bm after 4) -- 24 VGPRs more than without the pipeline;
-//   * issues the six pieces of tile t + 2 into stage t & 1, one after every fourth MFMA of the first half;
+// MAINLOOP (sp_gemm_glds_kernel_bf16x3).  256 x 256 workgroup tile, one workgroup per CU, 2 x 2 waves of 128 x 128
+// each, one per SIMD with all 512 registers: the 8 x 8 accumulator blocks of 16 x 16 fill the 256 AGPRs, the
+// fragments live in VGPRs.  k-tiles of 16 are brought by global_load_lds_dwordx4 into two LDS stages.  The MFMA is
+// v_mfma_f32_16x16x32_bf16 (under this loop the chip holds a higher clock on it than on 32x32x16: measured in
+// profiles/gemm_split_mfma_shape_notes.md), whose 32 k carry TWO terms of the same 16 k: lanes 0-31 of an operand
+// (k-groups 0, 1) hold the 16 k of one image, lanes 32-63 (k-groups 2, 3) the same 16 k of another.  Three MFMAs per
+// block and k-tile take the six products, smallest first, and inside an MFMA the smaller term first:
+//     Pa = A [l | h] . B [h | l] = al bh + ah bl,   Pb = A [m | h] . B [h | m] = am bh + ah bm,
+//     Pc = A [m | h] . B [m | h] = am bm + ah bh
+// -- two variants of every A block and three of every B block, 40 ds_read_b128 and 192 MFMAs per wave and k-tile.
+// The loop is software-pipelined one k-tile ahead IN REGISTERS: the MFMAs of k-tile t take every operand from VGPRs
+// that were filled during k-tile t - 1, so no LDS latency stands between the barrier and the first MFMA.  During
+// k-tile t a wave
+//   * issues the 192 MFMAs of tile t, Pa, Pb, Pc each over the 8 x 8 blocks;
+//   * reads the 40 fragments of tile t + 1 from stage (t + 1) & 1, one after every fourth MFMA: under Pa the A [m | h]
+//     and B [m | h] of Pc into a second register set (they are live to the last MFMA), under Pb the operands of Pa
+//     in place, under Pc the B [h | m] of Pb in place; the last read stands 35 MFMAs before the end;
+//   * issues its 12 pieces of tile t + 2 into stage t & 1, one after every eighth MFMA of the first half;
 // then waits for its pieces (vmcnt) AND its fragment reads (lgkmcnt) and meets the others at the one barrier per
 // k-tile.  That barrier publishes tile t + 2 and tells every wave that stage (t + 1) & 1 has been read, so the pieces
-// of tile t + 3 may overwrite it.  The loop is unrolled by two so that stages and register sets are constants; the
-// last tile but one issues no pieces, the last one no reads either.  The reads are asm with tied destinations (see
-// GS_READ_A).
-// An LDS image is [row][2 chunks of 16 B]; chunk q of row r lives in slot q ^ ((r >> 4) & 1): a ds_read_b128 is served
-// in groups of 16 lanes -- rows {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of a fragment's 32 -- and the banks repeat
-// every 8 rows of 32 B, so inside a group the rows below 16 and the rows from 16 on that share their banks are sent
-// to different halves of them: conflict-free.  A lane's fragment is 8 consecutive k of one row for both operands.
+// of tile t + 3 may overwrite it.  The loop is unrolled by two so that stages and register sets are constants, with
+// one more copy of the body for an odd count, and the body has no branch: the last two tiles request the last tile
+// again and the last one reads fragments nothing takes.  Reads and MFMAs are asm with tied destinations (see
+// GS_READ_A, GS_MFMA).
+// An LDS image is [row][2 chunks of 16 B]; chunk q of row r lives in slot q ^ ((r >> 4) & 1).  A fragment read takes
+// rows 16 blk .. 16 blk + 15 of one image in lanes 0-31 and of another in lanes 32-63, lane l chunk (l >> 4) & 1.  A
+// ds_read_b128 is served in lane groups {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31}: each takes rows {0-3, 12-15} at
+// one chunk and rows {4-11} at the other, 8 distinct rows mod 8 at each of the two slots, which are the 16 distinct
+// 16-byte units of the 256-byte bank period: conflict-free (SQ_LDS_BANK_CONFLICT = 0).
 #pragma once
+#include <utility>
 
 typedef __bf16 gs_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 gs_bf16x4 __attribute__((ext_vector_type(4)));
@@ -77,29 +94,34 @@ namespace {
 
 constexpr int GS_BK = 16;                         // k per k-tile
 constexpr int GS_RB = GS_BK * 2;                  // bytes of a row of a k-tile of one image
-constexpr int GS_WN = 4;                          // workgroup tile 256 x (64 GS_WN)
 constexpr unsigned GS_WIN_LO = (127u - 40u) << 23;   // bits of 2^-40
 constexpr unsigned GS_WIN_HI = (127u + 40u) << 23;   // bits of 2^40
 constexpr size_t GS_IMAGE_CAP = (size_t)2 << 30;  // bytes of operand images the tier may ask the workspace pool for
 constexpr size_t GS_WS_HEAD = 512;                // the flag, and room to align what follows
 
-template <int WN>
 struct GsCfg {
-  static constexpr int BM = 256, BN = 64 * WN, NW = 2 * WN, THREADS = 64 * NW;
+  static constexpr int BM = 256, BN = 256, NW = 4, THREADS = 64 * NW;   // 2 x 2 waves of 128 x 128
   static constexpr int A_BYTES = BM * GS_RB, B_BYTES = BN * GS_RB;      // one image of a k-tile
   static constexpr int STAGE_BYTES = 3 * A_BYTES + 3 * B_BYTES;         // Ah | Am | Al | Bh | Bm | Bl
   static constexpr int SMEM_BYTES = 2 * STAGE_BYTES;
   static constexpr int APW = A_BYTES / 1024 / NW, BPW = B_BYTES / 1024 / NW;   // 1-KiB pieces per wave and image
   static constexpr int NPIECES = 3 * APW + 3 * BPW;
-  static constexpr int SLOTS = SP_CUS * (WN == 4 ? 1 : 2);              // resident workgroups
+  static constexpr int SLOTS = SP_CUS;                                  // resident workgroups
+  static constexpr int NMFMA = 3 * 8 * 8;                               // per wave and k-tile
   static_assert(APW >= 1 && BPW >= 1 && APW * NW * 1024 == A_BYTES && BPW * NW * 1024 == B_BYTES, "tile / waves mismatch");
-  static_assert(NPIECES * 4 <= 48, "one piece after every fourth MFMA");
+  static_assert(NPIECES * 8 <= NMFMA / 2, "one piece after every eighth MFMA of the first half");
+  static_assert(STAGE_BYTES + 7 * 16 * GS_RB < 65536, "stage and block go into a ds_read's 16-bit offset");
 };
 
 template <int V>
 struct GsInt {                                    // a constant handed to a generic lambda
   static constexpr int value = V;
 };
+
+template <int... I, typename F>
+__device__ __forceinline__ void gs_unrolled(std::integer_sequence<int, I...>, F&& f) {   // f(GsInt<0>), f(GsInt<1>), ...
+  (f(GsInt<I>{}), ...);
+}
 
 __device__ __forceinline__ bool gs_outside(float v) {
   const unsigned b = __float_as_uint(v) & 0x7fffffffu;
@@ -201,12 +223,11 @@ __global__ __launch_bounds__(256) void sp_gemm_cut_cols_kernel(const float* __re
 // The mainloop.  Ah / Bh: the hi images, mid and lo `a_img` / `b_img` BYTES behind; KT k-tiles, `a_slab` / `b_slab` bytes
 // apart in an image: 32 x the rows the image was cut with, which is M / N, or more when Ah / Bh point at a row block of
 // the images of a larger operand.  flag_a / flag_b: the window flag of either operand's cut (they may be one word).
-template <int WN>
-__global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf16x3(
+__global__ __launch_bounds__(GsCfg::THREADS, 1) void sp_gemm_glds_kernel_bf16x3(
     const char* __restrict__ Ah, int64_t a_img, const char* __restrict__ Bh, int64_t b_img, float* __restrict__ C,
     int64_t ldc, int M, int N, int KT, int accumulate, int tiles_m, int tiles_n, int64_t a_slab, int64_t b_slab,
     const unsigned* __restrict__ flag_a, const unsigned* __restrict__ flag_b) {
-  using G = GsCfg<WN>;
+  using G = GsCfg;
   constexpr int APW = G::APW, BPW = G::BPW, NPIECES = G::NPIECES;
   extern __shared__ __attribute__((aligned(16))) char gs_smem[];
   if ((*flag_a | *flag_b) != 0u) return;                     // an operand left the window: the gated fp32 launch computes C
@@ -215,8 +236,8 @@ __global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf1
   const int m0 = tm * G::BM, n0 = tn * G::BN;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;                    // wm: which 128 rows, wn: which 64 columns
-  const int l31 = lane & 31, lh = lane >> 5;
+  const int wm = wid >> 1, wn = wid & 1;                     // wm: which 128 rows, wn: which 128 columns
+  const int l15 = lane & 15, lq = lane >> 4;                 // an operand's row / a result's column, and the k-group
 
   // ---- k-tile pieces: 1 KiB = one wave-wide 16-B load = 32 rows of one image; rows past the operand's end repeat
   // its last row (their results are masked on store)
@@ -254,76 +275,97 @@ __global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf1
     }                                                                                                  \
   } while (0)
 
-  f32x16 acc[4][2];
+  // The accumulators: 16 x 16 blocks, col = l15, row = 4 lq + r; 256 registers, all of the AGPRs.  The MFMA is asm with
+  // the accumulator tied ("+a"): left to the builtin, hipcc's allocator rotated the blocks through the AGPRs from MFMA
+  // to MFMA and spilled 940 registers.  What the compiler then no longer sees is the MFMA's latency, so the waits it
+  // would have inserted are stated: an accumulator is taken again 64 MFMAs later, GS_ACC_ZEROED puts the zeros in
+  // place before the prologue, and GS_ACC_DONE stands between the last MFMAs and the epilogue.
+  f32x4 acc[8][8];
+#define GS_MFMA(c, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b))
+#define GS_ACC_ZEROED(c) asm volatile("" : "+a"(c))
+#define GS_ACC_DONE(x)                                                                                              \
+  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3"                                                                      \
+               : "+a"(x[0]), "+a"(x[1]), "+a"(x[2]), "+a"(x[3]), "+a"(x[4]), "+a"(x[5]), "+a"(x[6]), "+a"(x[7]))
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    for (int j = 0; j < 8; ++j) {
+      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      GS_ACC_ZEROED(acc[i][j]);
+    }
 
-  // fragments: row (wave tile row + l31 [+ 32 i]), slot lh ^ ((row >> 4) & 1)
-  const int fslot = (lh ^ ((l31 >> 4) & 1)) * 16;
-  const int a_frag = (wm * 128 + l31) * GS_RB + fslot;
-  const int b_frag = 3 * G::A_BYTES + (wn * 64 + l31) * GS_RB + fslot;
-  const unsigned a_rd[2] = {s_base + (unsigned)a_frag, s_base + (unsigned)(G::STAGE_BYTES + a_frag)};   // per stage
-  const unsigned b_rd[2] = {s_base + (unsigned)b_frag, s_base + (unsigned)(G::STAGE_BYTES + b_frag)};
+  // A fragment is an operand of a 16x16x32 MFMA that carries two terms: k-groups 0, 1 (lanes 0-31) are the 16 k of one
+  // image, k-groups 2, 3 (lanes 32-63) the same 16 k of another.  Lane l reads row 16 blk + l15 of its image, chunk
+  // (lq & 1), which lies in slot (lq & 1) ^ (blk & 1).  One base register per variant and block parity; the stage and
+  // the block go into the read's offset.  Variants (image of lanes 0-31 | of lanes 32-63; 0 hi, 1 mid, 2 lo):
+  //   A: 0 = [l | h], 1 = [m | h];   B: 0 = [h | l], 1 = [h | m], 2 = [m | h]
+  const int up = lane >> 5;
+  unsigned a_rd[2][2], b_rd[3][2];
+#pragma unroll
+  for (int par = 0; par < 2; ++par) {
+    const unsigned a_row = s_base + (unsigned)((wm * 128 + l15) * GS_RB + (((lq & 1) ^ par) * 16));
+    const unsigned b_row = s_base + (unsigned)(3 * G::A_BYTES + (wn * 128 + l15) * GS_RB + (((lq & 1) ^ par) * 16));
+    a_rd[0][par] = a_row + (unsigned)((up ? 0 : 2) * G::A_BYTES);
+    a_rd[1][par] = a_row + (unsigned)((up ? 0 : 1) * G::A_BYTES);
+    b_rd[0][par] = b_row + (unsigned)((up ? 2 : 0) * G::B_BYTES);
+    b_rd[1][par] = b_row + (unsigned)((up ? 1 : 0) * G::B_BYTES);
+    b_rd[2][par] = b_row + (unsigned)((up ? 0 : 1) * G::B_BYTES);
+  }
 
-  // The fragments of k-tile t: mid and lo in one set of registers, which tile t + 1 refills as the term order frees
-  // them; hi is live to the last term, so it has two sets and tile t uses set t & 1.
-  gs_bf16x8 am[4], al[4], bm[2], bl[2], ah[2][4], bh[2][2];
-  // A fragment read, image p_ (0 hi, 1 mid, 2 lo) of stage s_, into `dst`.  Written in asm with the destination tied
+  // The fragments of k-tile t.  a_lh, b_hl and b_hm are one set of registers, which tile t + 1 refills once the term
+  // that takes them is through; a_mh and b_mh are live to the last MFMA, so they have two sets and tile t uses set
+  // t & 1.
+  gs_bf16x8 a_lh[8], b_hl[8], b_hm[8], a_mh[2][8], b_mh[2][8];
+  // A fragment read, variant v_ of stage s_, block blk_, into `dst`.  Written in asm with the destination tied
   // ("+v"): the new fragment goes into the very registers of the old one, which hipcc's allocator does not find by
   // itself (it took fresh registers for the next tile and spilled).  The compiler then does not count these reads in
   // lgkmcnt, so GS_READS_DONE states the wait, and passes every fragment through it: no MFMA that takes one can be
   // moved in front of the wait.
-#define GS_READ_A(dst, s_, p_, i_) \
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(a_rd[s_]), "n"((p_) * G::A_BYTES + (i_) * 32 * GS_RB) : "memory")
-#define GS_READ_B(dst, s_, p_, j_) \
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(b_rd[s_]), "n"((p_) * G::B_BYTES + (j_) * 32 * GS_RB) : "memory")
-#define GS_READS_DONE(s_)                                                                                             \
-  do {                                                                                                                \
-    asm volatile("s_waitcnt lgkmcnt(0)"                                                                               \
-                 : "+v"(al[0]), "+v"(al[1]), "+v"(al[2]), "+v"(al[3]), "+v"(am[0]), "+v"(am[1]), "+v"(am[2]),          \
-                   "+v"(am[3]), "+v"(bl[0]), "+v"(bl[1]), "+v"(bm[0]), "+v"(bm[1])                                     \
-                 :: "memory");                                                                                        \
-    asm volatile("" : "+v"(ah[s_][0]), "+v"(ah[s_][1]), "+v"(ah[s_][2]), "+v"(ah[s_][3]), "+v"(bh[s_][0]),             \
-                      "+v"(bh[s_][1]) :: "memory");                                                                   \
+#define GS_READ_A(dst, s_, v_, blk_)                                       \
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(a_rd[v_][(blk_) & 1]), \
+               "n"((s_) * G::STAGE_BYTES + (blk_) * 16 * GS_RB) : "memory")
+#define GS_READ_B(dst, s_, v_, blk_)                                       \
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(b_rd[v_][(blk_) & 1]), \
+               "n"((s_) * G::STAGE_BYTES + (blk_) * 16 * GS_RB) : "memory")
+#define GS_TIE8(x) "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])
+#define GS_READS_DONE(s_)                                                                              \
+  do {                                                                                                 \
+    asm volatile("s_waitcnt lgkmcnt(0)" : GS_TIE8(a_lh), GS_TIE8(b_hl), GS_TIE8(b_hm) :: "memory");    \
+    asm volatile("" : GS_TIE8(a_mh[s_]), GS_TIE8(b_mh[s_]) :: "memory");                               \
   } while (0)
 
-  // One k-tile: its 48 MFMAs -- al bh, ah bl, am bm, am bh, ah bm, ah bh for the 4 x 2 tiles of the wave -- from
-  // registers alone.  In the gaps between them, if `rd`, the 18 fragment reads of tile t + 1 from stage (t + 1) & 1
-  // (at most one per gap: hi into the other set first, then lo and mid behind the last MFMA that reads the registers
-  // they go to; the last one 6 MFMAs before the end), and if `ld`, a piece of the request for tile t + 2 into stage
-  // t & 1 after every fourth.  `par` is t & 1 as a constant: stages and register sets are then fixed per copy of the
-  // body, and nothing is moved between the sets.
-  auto ktile = [&](auto par_, const bool rd, const bool ld, int t) __attribute__((always_inline)) {
+  // One k-tile: its 192 MFMAs -- Pa = [l | h] [h | l], Pb = [m | h] [h | m], Pc = [m | h] [m | h], each over the 8 x 8
+  // blocks of the wave -- from registers alone.  In the gaps between them, the 40 fragment reads of tile t + 1 from
+  // stage (t + 1) & 1, one after every fourth MFMA: under Pa the 16 fragments Pc takes, into the other set; under Pb
+  // the 16 of Pa, in place; under Pc the 8 that only Pb takes, in place (the last one 35 MFMAs before the end); and
+  // a piece of the request for tile t + 2 into stage t & 1 after every eighth MFMA of the first half.  The body has
+  // no branch: the last two tiles request the last tile once more, and the last one reads fragments that nothing
+  // takes, both inside the operands' images and the two stages.  `par` is t & 1 as a constant: stages and register
+  // sets are then fixed per copy of the body, and nothing is moved between the sets.
+  auto ktile = [&](auto par_, int t) __attribute__((always_inline)) {
     constexpr int CUR = decltype(par_)::value, NXT = CUR ^ 1;
-    const int64_t ka_ = (int64_t)(t + 2) * a_slab, kb_ = (int64_t)(t + 2) * b_slab;
+    const int tl = t + 2 < KT ? t + 2 : KT - 1;
+    const int64_t ka_ = (int64_t)tl * a_slab, kb_ = (int64_t)tl * b_slab;
     const unsigned st_ = s_base + (unsigned)CUR * G::STAGE_BYTES;
-#pragma unroll
-    for (int idx = 0; idx < 48; ++idx) {
-      const int term = idx >> 3, i = (idx & 7) >> 1, j = idx & 1;
-      const gs_bf16x8 a = term == 0 ? al[i] : (term == 2 || term == 3) ? am[i] : ah[CUR][i];
-      const gs_bf16x8 b = term == 1 ? bl[j] : (term == 2 || term == 4) ? bm[j] : bh[CUR][j];
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[i][j], 0, 0, 0);
+    gs_unrolled(std::make_integer_sequence<int, G::NMFMA>{}, [&](auto idx_) __attribute__((always_inline)) {
+      constexpr int idx = decltype(idx_)::value, term = idx >> 6, i = (idx >> 3) & 7, j = idx & 7;
+      const gs_bf16x8 a = term == 0 ? a_lh[i] : a_mh[CUR][i];
+      const gs_bf16x8 b = term == 0 ? b_hl[j] : term == 1 ? b_hm[j] : b_mh[CUR][j];
+      GS_MFMA(acc[i][j], a, b);
       __builtin_amdgcn_sched_barrier(0);
-      if (rd) {
-        const int q = idx & 7, r = q < 3 ? q : q - 1;          // gaps 0 1 2 4 [5 6] of a term; 3 and 7 may hold a piece
-        if (term == 0 && q != 3 && q != 7) {
-          if (r < 4) GS_READ_A(ah[NXT][r & 3], NXT, 0, r & 3);
-          else GS_READ_B(bh[NXT][r & 1], NXT, 0, r & 1);
-        }
-        if (term == 1 && q != 3 && r < 4) GS_READ_A(al[r & 3], NXT, 2, r & 3);      // al: free after term 0
-        if (term == 2 && q < 2) GS_READ_B(bl[q & 1], NXT, 2, q & 1);                // bl: after term 1
-        if (term == 4 && q < 4) GS_READ_A(am[q & 3], NXT, 1, q & 3);                // am: after term 3
-        if (term == 5 && q < 2) GS_READ_B(bm[q & 1], NXT, 1, q & 1);                // bm: after term 4
+      if constexpr ((idx & 3) == 0) {
+        constexpr int q = (idx & 63) >> 2, blk = q & 7;        // the 16 read gaps of a term
+        if constexpr (term == 0 && q < 8) GS_READ_A(a_mh[NXT][blk], NXT, 1, blk);
+        if constexpr (term == 0 && q >= 8) GS_READ_B(b_mh[NXT][blk], NXT, 2, blk);
+        if constexpr (term == 1 && q < 8) GS_READ_A(a_lh[blk], NXT, 0, blk);        // a_lh, b_hl: free after Pa
+        if constexpr (term == 1 && q >= 8) GS_READ_B(b_hl[blk], NXT, 0, blk);
+        if constexpr (term == 2 && q < 8) GS_READ_B(b_hm[blk], NXT, 1, blk);        // b_hm: after Pb
       }
-      if (ld && idx % 4 == 3 && idx / 4 < NPIECES) GS_PIECE(idx / 4);
+      if constexpr (idx % 8 == 7 && idx / 8 < NPIECES) GS_PIECE(idx / 8);
       __builtin_amdgcn_sched_barrier(0);
-    }
-    if (ld) SP_GLDS_LANDED();
-    if (rd) GS_READS_DONE(NXT);
+    });
+    SP_GLDS_LANDED();
+    GS_READS_DONE(NXT);
     // tile t + 2 has landed in stage t & 1, and this wave's reads of stage (t + 1) & 1 have returned, before any
     // wave's pieces for tile t + 3 may overwrite it
     __syncthreads();
@@ -341,25 +383,20 @@ __global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf1
   }
   SP_GLDS_LANDED();
   __syncthreads();
-  if (KT > 1) {
-    const int64_t ka_ = a_slab, kb_ = b_slab;
+  {
+    const int64_t ka_ = KT > 1 ? a_slab : 0, kb_ = KT > 1 ? b_slab : 0;
     const unsigned st_ = s_base + G::STAGE_BYTES;
 #pragma unroll
     for (int i = 0; i < NPIECES; ++i) GS_PIECE(i);
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ah[0][i] = ah[1][i] = am[i] = al[i] = gs_bf16x8{};
-    GS_READ_A(ah[0][i], 0, 0, i);
-    GS_READ_A(am[i], 0, 1, i);
-    GS_READ_A(al[i], 0, 2, i);
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    bh[0][j] = bh[1][j] = bm[j] = bl[j] = gs_bf16x8{};
-    GS_READ_B(bh[0][j], 0, 0, j);
-    GS_READ_B(bm[j], 0, 1, j);
-    GS_READ_B(bl[j], 0, 2, j);
+  for (int blk = 0; blk < 8; ++blk) {
+    a_lh[blk] = a_mh[0][blk] = a_mh[1][blk] = b_hl[blk] = b_hm[blk] = b_mh[0][blk] = b_mh[1][blk] = gs_bf16x8{};
+    GS_READ_A(a_lh[blk], 0, 0, blk);
+    GS_READ_A(a_mh[0][blk], 0, 1, blk);
+    GS_READ_B(b_hl[blk], 0, 0, blk);
+    GS_READ_B(b_hm[blk], 0, 1, blk);
+    GS_READ_B(b_mh[0][blk], 0, 2, blk);
   }
   SP_GLDS_LANDED();
   GS_READS_DONE(0);
@@ -368,29 +405,39 @@ __global__ __launch_bounds__(GsCfg<WN>::THREADS, 2) void sp_gemm_glds_kernel_bf1
   // two k-tiles per trip, then the last one of an odd count
   int t = 0;
   for (; t + 1 < KT; t += 2) {
-    ktile(even, true, t + 2 < KT, t);
-    ktile(odd, t + 2 < KT, t + 3 < KT, t + 1);
+    ktile(even, t);
+    ktile(odd, t + 1);
   }
-  if (t < KT) ktile(even, false, false, t);
+  if (t < KT) ktile(even, t);
+  GS_ACC_DONE(acc[7]);                       // the last eight MFMAs wrote row 7; the pipe is in order, so all are through
+#undef GS_MFMA
+#undef GS_ACC_ZEROED
+#undef GS_ACC_DONE
 #undef GS_READ_A
 #undef GS_READ_B
 #undef GS_READS_DONE
+#undef GS_TIE8
 #undef GS_PIECE
 
-  // ---- epilogue (as sp_gemm_glds_kernel's): C/D layout col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  // ---- epilogue: C/D layout col = lane & 15, row = 4 (lane >> 4) + r.  A block alone writes 64-byte half-lines, so
+  // blocks j and j + 1 of a row go out back to back: a row's 32 consecutive floats leave together.
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < 8; ++i) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + wn * 64 + j * 32 + l31;
+    for (int jp = 0; jp < 8; jp += 2) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row < M && col < N) {
-          float* p = C + (int64_t)row * ldc + col;
-          float v = acc[i][j][r];
-          if (accumulate) v += *p;
-          *p = v;
+      for (int r = 0; r < 4; ++r) {
+        const int row = m0 + wm * 128 + i * 16 + 4 * lq + r;
+#pragma unroll
+        for (int j = jp; j < jp + 2; ++j) {
+          const int col = n0 + wn * 128 + j * 16 + l15;
+          if (row < M && col < N) {
+            float* p = C + (int64_t)row * ldc + col;
+            float v;                       // (read where it is stored: hipcc otherwise copies all 256 at once and spills)
+            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(acc[i][j][r]));
+            if (accumulate) v += *p;
+            *p = v;
+          }
         }
       }
     }
@@ -422,7 +469,7 @@ static bool sp_gemm_bf16_plan(int64_t M, int64_t N, int64_t K) {
     const char* e = getenv("SP_GEMM_SPLIT");
     mode = e ? atoi(e) : 1;
   }
-  using G = GsCfg<GS_WN>;
+  using G = GsCfg;
   if (mode == 0 || K < 16 || N % 4 != 0 || N < 4 || M < 1 || M > 2147483647LL || N > 2147483647LL || K > 2147483647LL)
     return false;
   const int64_t tb = ((M + 255) / 256) * ((N + 127) / 128);
@@ -474,10 +521,10 @@ static void sp_gemm_bf16_cut(int side, const float* X, int64_t ld, int64_t rows,
 static int sp_gemm_bf16_launch(const float* A, int64_t lda, const char* imgA, int64_t a_rows, int64_t a_row0,
                                const float* B, int64_t ldb, const char* imgB, int64_t b_rows, int64_t b_row0, float* C,
                                int64_t ldc, int64_t M, int64_t N, int64_t K, int acc, void* ws, hipStream_t st) {
-  using G = GsCfg<GS_WN>;
+  using G = GsCfg;
   const int64_t KT = (K + GS_BK - 1) / GS_BK;
   const int64_t tiles_m = (M + G::BM - 1) / G::BM, tiles_n = (N + G::BN - 1) / G::BN;
-  auto kern = sp_gemm_glds_kernel_bf16x3<GS_WN>;
+  auto kern = sp_gemm_glds_kernel_bf16x3;
   using FCfg = GldsCfg<256, 128, 2, 2>;
   auto gated = sp_gemm_f32_gated_kernel<FCfg, 256, 128, 2, 2, 2>;
   static bool attr_set = false;
