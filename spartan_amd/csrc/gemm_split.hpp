@@ -75,10 +75,22 @@
 //   * issues its 12 pieces of tile t + 2 into stage t & 1, one after every eighth MFMA of the first half;
 // then waits for its pieces (vmcnt) AND its fragment reads (lgkmcnt) and meets the others at the one barrier per
 // k-tile.  That barrier publishes tile t + 2 and tells every wave that stage (t + 1) & 1 has been read, so the pieces
-// of tile t + 3 may overwrite it.  The loop is unrolled by two so that stages and register sets are constants, with
-// one more copy of the body for an odd count, and the body has no branch: the last two tiles request the last tile
-// again and the last one reads fragments nothing takes.  Reads and MFMAs are asm with tied destinations (see
-// GS_READ_A, GS_MFMA).
+// of tile t + 3 may overwrite it.  The loop is unrolled by two so that stages and register sets are constants.
+// Every gap between two MFMAs is written to an ISSUE BUDGET of 16 cycles, the MFMA's own 8 included (by the issue
+// prices measured for MI355X: costs add, and a gap runs max(16, their sum); the prices are not re-measured here, the
+// kernel's cycles are), so a gap holds the MFMA and at most one of: a fragment read; a piece's load, alone;
+// that piece's write of M0 (one s_add_u32 of a constant to the wave's LDS base), one gap EARLIER, so that the MFMA
+// between them is the wait state the load needs behind it; the advance of one image's running 64-bit base by a slab
+// (s_add_u32 / s_addc_u32), two gaps behind the image's last piece.  There is no multiply, no clamp and no other
+// scalar work in the body, and nothing between the barrier and the next MFMA but the trip count of the two-k-tile
+// loop.  The clamp min(t + 2, KT - 1) of the requested k-tile is in the code's shape instead: the loop runs k-tiles
+// 0 .. KT - 3, and the last two are copies of the body whose bases stand on the last k-tile and do not advance -- they
+// request it again, and the last one reads fragments nothing takes, both inside the images and the stages, so no
+// body has a branch.  Reads and MFMAs are asm with tied destinations (see GS_READ_A, GS_MFMA).
+// Measured and not kept (profiles/gemm_split_issue_budget_notes.md): an epilogue whose interior tiles store without a
+// predicate and whose `accumulate` copy loads eight values per wait (no gain beyond the run-to-run spread, on the
+// headline or on the K-split rows), and one persistent workgroup per CU whose last two k-tiles request the first two
+// of its next tile (slower).
 // An LDS image is [row][2 chunks of 16 B]; chunk q of row r lives in slot q ^ ((r >> 4) & 1).  A fragment read takes
 // rows 16 blk .. 16 blk + 15 of one image in lanes 0-31 and of another in lanes 32-63, lane l chunk (l >> 4) & 1.  A
 // ds_read_b128 is served in lane groups {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31}: each takes rows {0-3, 12-15} at
@@ -229,11 +241,10 @@ __global__ __launch_bounds__(GsCfg::THREADS, 1) void sp_gemm_glds_kernel_bf16x3(
     const unsigned* __restrict__ flag_a, const unsigned* __restrict__ flag_b) {
   using G = GsCfg;
   constexpr int APW = G::APW, BPW = G::BPW, NPIECES = G::NPIECES;
+  static_assert(APW == BPW, "the six images of a request take the same number of pieces");
+  constexpr int PW = APW;
   extern __shared__ __attribute__((aligned(16))) char gs_smem[];
   if ((*flag_a | *flag_b) != 0u) return;                     // an operand left the window: the gated fp32 launch computes C
-  int tm, tn;
-  sp_gemm_tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n, tm, tn);
-  const int m0 = tm * G::BM, n0 = tn * G::BN;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;                     // wm: which 128 rows, wn: which 128 columns
@@ -241,58 +252,43 @@ __global__ __launch_bounds__(GsCfg::THREADS, 1) void sp_gemm_glds_kernel_bf16x3(
 
   // ---- k-tile pieces: 1 KiB = one wave-wide 16-B load = 32 rows of one image; rows past the operand's end repeat
   // its last row (their results are masked on store)
-  unsigned a_off[APW], b_off[BPW];
+  auto piece_offsets = [&](int r0, int rows, unsigned (&off)[PW]) __attribute__((always_inline)) {
 #pragma unroll
-  for (int j = 0; j < APW; ++j) {
-    const int slot = (wid * APW + j) * 64 + lane;
-    int row = slot >> 1;
-    const int q = (slot & 1) ^ ((row >> 4) & 1);
-    if (m0 + row > M - 1) row = M - 1 - m0;
-    a_off[j] = (unsigned)(row * GS_RB + q * 16);
-  }
-#pragma unroll
-  for (int j = 0; j < BPW; ++j) {
-    const int slot = (wid * BPW + j) * 64 + lane;
-    int row = slot >> 1;
-    const int q = (slot & 1) ^ ((row >> 4) & 1);
-    if (n0 + row > N - 1) row = N - 1 - n0;
-    b_off[j] = (unsigned)(row * GS_RB + q * 16);
-  }
-  const char* __restrict__ Ablk = Ah + (int64_t)m0 * GS_RB;
-  const char* __restrict__ Bblk = Bh + (int64_t)n0 * GS_RB;
+    for (int j = 0; j < PW; ++j) {
+      const int slot = (wid * PW + j) * 64 + lane;
+      int row = slot >> 1;
+      const int q = (slot & 1) ^ ((row >> 4) & 1);
+      if (r0 + row > rows - 1) row = rows - 1 - r0;
+      off[j] = (unsigned)(row * GS_RB + q * 16);
+    }
+  };
   const unsigned s_base = SP_LDS_ADDR(gs_smem);
 
-  // piece i of the request for k-tile kt_ into stage st_: image i / (APW or BPW) of A, then of B
-#define GS_PIECE(i)                                                                                    \
-  do {                                                                                                 \
-    if ((i) < 3 * APW) {                                                                               \
-      const int p_ = (i) / APW, j_ = (i) % APW;                                                        \
-      SP_GLDS_S(Ablk + p_ * a_img + ka_, a_off[j_], st_ + p_ * G::A_BYTES + (wid * APW + j_) * 1024);  \
-    } else {                                                                                           \
-      const int p_ = ((i) - 3 * APW) / BPW, j_ = ((i) - 3 * APW) % BPW;                                \
-      SP_GLDS_S(Bblk + p_ * b_img + kb_, b_off[j_],                                                    \
-                st_ + 3 * G::A_BYTES + p_ * G::B_BYTES + (wid * BPW + j_) * 1024);                     \
-    }                                                                                                  \
-  } while (0)
+  // A request is 12 pieces: image i / PW of A, then of B.  Piece i goes out in two asm statements, in two MFMA gaps:
+  // GS_PIECE_M0 writes its LDS target to M0, GS_PIECE_LOAD is the load, and the MFMA between them is the wait state
+  // an LDS-DMA needs behind a write of M0.  `asm volatile` keeps them in order and the write names M0 as clobbered;
+  // the load's use of M0 cannot be stated, so nothing the compiler generates between the two may write M0 (none does:
+  // read in the ISA of the loop and the prologue), and this kernel must not use the global_load_lds builtin.  M0 is
+  // the wave's first piece of stage 0 plus a constant, in one s_add_u32: a table of the 24 targets would take 24 SGPRs.
+  const unsigned s_wave = s_base + (unsigned)(wid * PW) * 1024u;
+#define GS_PIECE_LDS(stage_, i) \
+  ((stage_) * G::STAGE_BYTES + ((i) < 3 * PW ? 0 : 3 * G::A_BYTES) + (((i) / PW) % 3) * G::A_BYTES + ((i) % PW) * 1024)
+#define GS_PIECE_M0(stage_, i) \
+  asm volatile("s_add_u32 m0, %0, %1" ::"s"(s_wave), "n"(GS_PIECE_LDS(stage_, i)) : "memory", "scc", "m0")
+#define GS_PIECE_LOAD(base, voff) asm volatile("global_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base) : "memory")
+  static_assert(G::A_BYTES == G::B_BYTES, "GS_PIECE_LDS strides both operands' images by A_BYTES");
 
   // The accumulators: 16 x 16 blocks, col = l15, row = 4 lq + r; 256 registers, all of the AGPRs.  The MFMA is asm with
   // the accumulator tied ("+a"): left to the builtin, hipcc's allocator rotated the blocks through the AGPRs from MFMA
   // to MFMA and spilled 940 registers.  What the compiler then no longer sees is the MFMA's latency, so the waits it
   // would have inserted are stated: an accumulator is taken again 64 MFMAs later, GS_ACC_ZEROED puts the zeros in
-  // place before the prologue, and GS_ACC_DONE stands between the last MFMAs and the epilogue.
+  // place before a tile's first fragment reads, and GS_ACC_DONE stands between the last MFMAs and the epilogue.
   f32x4 acc[8][8];
 #define GS_MFMA(c, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b))
 #define GS_ACC_ZEROED(c) asm volatile("" : "+a"(c))
 #define GS_ACC_DONE(x)                                                                                              \
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3"                                                                      \
                : "+a"(x[0]), "+a"(x[1]), "+a"(x[2]), "+a"(x[3]), "+a"(x[4]), "+a"(x[5]), "+a"(x[6]), "+a"(x[7]))
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      GS_ACC_ZEROED(acc[i][j]);
-    }
 
   // A fragment is an operand of a 16x16x32 MFMA that carries two terms: k-groups 0, 1 (lanes 0-31) are the 16 k of one
   // image, k-groups 2, 3 (lanes 32-63) the same 16 k of another.  Lane l reads row 16 blk + l15 of its image, chunk
@@ -327,6 +323,13 @@ __global__ __launch_bounds__(GsCfg::THREADS, 1) void sp_gemm_glds_kernel_bf16x3(
 #define GS_READ_B(dst, s_, v_, blk_)                                       \
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(b_rd[v_][(blk_) & 1]), \
                "n"((s_) * G::STAGE_BYTES + (blk_) * 16 * GS_RB) : "memory")
+  // (a tile's first fill: nothing is in the registers yet, so the destination is an output only, and the set the
+  // first k-tile refills is merely declared written)
+#define GS_FILL_A(dst, v_, blk_) \
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(a_rd[v_][(blk_) & 1]), "n"((blk_) * 16 * GS_RB) : "memory")
+#define GS_FILL_B(dst, v_, blk_) \
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(b_rd[v_][(blk_) & 1]), "n"((blk_) * 16 * GS_RB) : "memory")
+#define GS_FILL_NONE(dst) asm volatile("" : "=v"(dst))
 #define GS_TIE8(x) "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])
 #define GS_READS_DONE(s_)                                                                              \
   do {                                                                                                 \
@@ -335,18 +338,22 @@ __global__ __launch_bounds__(GsCfg::THREADS, 1) void sp_gemm_glds_kernel_bf16x3(
   } while (0)
 
   // One k-tile: its 192 MFMAs -- Pa = [l | h] [h | l], Pb = [m | h] [h | m], Pc = [m | h] [m | h], each over the 8 x 8
-  // blocks of the wave -- from registers alone.  In the gaps between them, the 40 fragment reads of tile t + 1 from
-  // stage (t + 1) & 1, one after every fourth MFMA: under Pa the 16 fragments Pc takes, into the other set; under Pb
-  // the 16 of Pa, in place; under Pc the 8 that only Pb takes, in place (the last one 35 MFMAs before the end); and
-  // a piece of the request for tile t + 2 into stage t & 1 after every eighth MFMA of the first half.  The body has
-  // no branch: the last two tiles request the last tile once more, and the last one reads fragments that nothing
-  // takes, both inside the operands' images and the two stages.  `par` is t & 1 as a constant: stages and register
-  // sets are then fixed per copy of the body, and nothing is moved between the sets.
-  auto ktile = [&](auto par_, int t) __attribute__((always_inline)) {
+  // blocks of the wave -- from registers alone.  Every gap between two MFMAs has an issue budget of 16 cycles, 8 of
+  // them the MFMA's own, and holds at most one of:
+  //   * a fragment read of tile t + 1 from stage (t + 1) & 1, after every fourth MFMA: under Pa the 16 fragments Pc
+  //     takes, into the other set; under Pb the 16 of Pa, in place; under Pc the 8 that only Pb takes, in place (the
+  //     last one 35 MFMAs before the end);
+  //   * a piece of the request into stage t & 1, after MFMA 8 i + 7 of the first half, and nothing else;
+  //   * that piece's write of M0, one gap earlier;
+  //   * the advance of an image's running base (one s_add_u32 / s_addc_u32), two gaps behind the image's last piece.
+  // What is requested is the caller's: `pa` / `pb` are the running bases of the six images, at the k-tile to bring,
+  // `oa` / `ob` the lanes' offsets, `ia` / `ib` what the bases advance by.  The steady body asks for k-tile t + 2 and
+  // advances by a slab; the last two k-tiles ask for the last one again and stand still (below).  The body has no
+  // branch, no multiply and no scalar work in front of its first MFMA.  `par` is t & 1 as a constant: stages and
+  // register sets are then fixed per copy of the body, and nothing is moved between the sets.
+  auto ktile = [&](auto par_, const char* (&pa)[3], const char* (&pb)[3], const unsigned (&oa)[PW],
+                   const unsigned (&ob)[PW], int64_t ia, int64_t ib) __attribute__((always_inline)) {
     constexpr int CUR = decltype(par_)::value, NXT = CUR ^ 1;
-    const int tl = t + 2 < KT ? t + 2 : KT - 1;
-    const int64_t ka_ = (int64_t)tl * a_slab, kb_ = (int64_t)tl * b_slab;
-    const unsigned st_ = s_base + (unsigned)CUR * G::STAGE_BYTES;
     gs_unrolled(std::make_integer_sequence<int, G::NMFMA>{}, [&](auto idx_) __attribute__((always_inline)) {
       constexpr int idx = decltype(idx_)::value, term = idx >> 6, i = (idx >> 3) & 7, j = idx & 7;
       const gs_bf16x8 a = term == 0 ? a_lh[i] : a_mh[CUR][i];
@@ -361,87 +368,162 @@ __global__ __launch_bounds__(GsCfg::THREADS, 1) void sp_gemm_glds_kernel_bf16x3(
         if constexpr (term == 1 && q >= 8) GS_READ_B(b_hl[blk], NXT, 0, blk);
         if constexpr (term == 2 && q < 8) GS_READ_B(b_hm[blk], NXT, 1, blk);        // b_hm: after Pb
       }
-      if constexpr (idx % 8 == 7 && idx / 8 < NPIECES) GS_PIECE(idx / 8);
+      if constexpr (idx % 8 == 6 && idx / 8 < NPIECES) GS_PIECE_M0(CUR, idx / 8);
+      if constexpr (idx % 8 == 7 && idx / 8 < NPIECES) {
+        constexpr int pc = idx / 8, img = pc / PW;
+        if constexpr (img < 3) GS_PIECE_LOAD(pa[img], oa[pc % PW]);
+        else GS_PIECE_LOAD(pb[img - 3], ob[pc % PW]);
+      }
+      if constexpr (idx % (8 * PW) == 1 && idx / (8 * PW) >= 1 && idx / (8 * PW) <= 6) {
+        constexpr int img = idx / (8 * PW) - 1;
+        if constexpr (img < 3) {
+          pa[img] += ia;
+          asm volatile("" : "+s"(pa[img]));
+        } else {
+          pb[img - 3] += ib;
+          asm volatile("" : "+s"(pb[img - 3]));
+        }
+      }
       __builtin_amdgcn_sched_barrier(0);
     });
     SP_GLDS_LANDED();
     GS_READS_DONE(NXT);
-    // tile t + 2 has landed in stage t & 1, and this wave's reads of stage (t + 1) & 1 have returned, before any
-    // wave's pieces for tile t + 3 may overwrite it
+    // the request has landed in stage t & 1, and this wave's reads of stage (t + 1) & 1 have returned, before any
+    // wave's next pieces may overwrite it
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
   };
   GsInt<0> even;
   GsInt<1> odd;
 
-  // prologue: tile 0 lands and is published; tile 1's request goes out whole; tile 0's fragments are read
-  {
-    const int64_t ka_ = 0, kb_ = 0;
-    const unsigned st_ = s_base;
+  // ---- the tile.  Written once and instantiated per parity of the count of k-tiles, prologue and epilogue included:
+  // with both sequences of bodies behind one loop, or with the two paths joined again in front of one epilogue, hipcc's
+  // allocator has to reconcile two assignments of the 480 live registers and spills (3652 and 754 VGPRs).
+  auto tile = [&](auto odd_count_) __attribute__((always_inline)) {
+    constexpr bool ODD = decltype(odd_count_)::value != 0;
+    int tm, tn;
+    sp_gemm_tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n, tm, tn);
+    const int m0 = tm * G::BM, n0 = tn * G::BN;
+    unsigned a_off[PW], b_off[PW];
+    piece_offsets(m0, M, a_off);
+    piece_offsets(n0, N, b_off);
+    const char *ra[3], *rb[3];                               // the images' running bases, at the k-tile to request
 #pragma unroll
-    for (int i = 0; i < NPIECES; ++i) GS_PIECE(i);
-  }
-  SP_GLDS_LANDED();
-  __syncthreads();
-  {
-    const int64_t ka_ = KT > 1 ? a_slab : 0, kb_ = KT > 1 ? b_slab : 0;
-    const unsigned st_ = s_base + G::STAGE_BYTES;
+    for (int p = 0; p < 3; ++p) {
+      ra[p] = Ah + (int64_t)m0 * GS_RB + p * a_img;
+      rb[p] = Bh + (int64_t)n0 * GS_RB + p * b_img;
+    }
 #pragma unroll
-    for (int i = 0; i < NPIECES; ++i) GS_PIECE(i);
-  }
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-  for (int blk = 0; blk < 8; ++blk) {
-    a_lh[blk] = a_mh[0][blk] = a_mh[1][blk] = b_hl[blk] = b_hm[blk] = b_mh[0][blk] = b_mh[1][blk] = gs_bf16x8{};
-    GS_READ_A(a_lh[blk], 0, 0, blk);
-    GS_READ_A(a_mh[0][blk], 0, 1, blk);
-    GS_READ_B(b_hl[blk], 0, 0, blk);
-    GS_READ_B(b_hm[blk], 0, 1, blk);
-    GS_READ_B(b_mh[0][blk], 0, 2, blk);
-  }
-  SP_GLDS_LANDED();
-  GS_READS_DONE(0);
-  __syncthreads();
+      for (int j = 0; j < 8; ++j) {
+        acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        GS_ACC_ZEROED(acc[i][j]);
+      }
+    // prologue: k-tile 0 lands and is published; k-tile 1's request goes out whole; k-tile 0's fragments are read
+    gs_unrolled(std::make_integer_sequence<int, 2 * NPIECES>{}, [&](auto n_) __attribute__((always_inline)) {
+      constexpr int s = decltype(n_)::value / NPIECES, i = decltype(n_)::value % NPIECES;
+      GS_PIECE_M0(s, i);
+      asm volatile("s_nop 0");                               // (no MFMA stands between the two here)
+      if constexpr (i < 3 * PW) GS_PIECE_LOAD(ra[i / PW], a_off[i % PW]);
+      else GS_PIECE_LOAD(rb[i / PW - 3], b_off[i % PW]);
+      if constexpr (i == NPIECES - 1) {
+        if constexpr (s == 0) {
+          SP_GLDS_LANDED();
+          __syncthreads();
+        }
+        const int64_t da = s == 0 && KT < 2 ? 0 : a_slab, db = s == 0 && KT < 2 ? 0 : b_slab;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+          ra[p] += da;                                       // (after both: k-tile 2, which only KT >= 3 requests)
+          rb[p] += db;
+        }
+      }
+    });
+#pragma unroll
+    for (int blk = 0; blk < 8; ++blk) {
+      GS_FILL_A(a_lh[blk], 0, blk);
+      GS_FILL_A(a_mh[0][blk], 1, blk);
+      GS_FILL_B(b_hl[blk], 0, blk);
+      GS_FILL_B(b_hm[blk], 1, blk);
+      GS_FILL_B(b_mh[0][blk], 2, blk);
+      GS_FILL_NONE(a_mh[1][blk]);
+      GS_FILL_NONE(b_mh[1][blk]);
+    }
+    SP_GLDS_LANDED();
+    GS_READS_DONE(0);
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
 
-  // two k-tiles per trip, then the last one of an odd count
-  int t = 0;
-  for (; t + 1 < KT; t += 2) {
-    ktile(even, t);
-    ktile(odd, t + 1);
-  }
-  if (t < KT) ktile(even, t);
-  GS_ACC_DONE(acc[7]);                       // the last eight MFMAs wrote row 7; the pipe is in order, so all are through
+    // k-tiles 0 .. KT - 3 request k-tile t + 2 and step on by a slab, two per trip (and one more for an odd count);
+    // the last two request the last k-tile once more, with no step: the clamp of t + 2 costs the loop nothing
+    for (int n = (KT - 2) >> 1; n > 0; --n) {
+      ktile(even, ra, rb, a_off, b_off, a_slab, b_slab);
+      ktile(odd, ra, rb, a_off, b_off, a_slab, b_slab);
+    }
+    const auto last_ktile = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        ra[p] = Ah + (int64_t)m0 * GS_RB + p * a_img + (int64_t)(KT - 1) * a_slab;
+        rb[p] = Bh + (int64_t)n0 * GS_RB + p * b_img + (int64_t)(KT - 1) * b_slab;
+      }
+    };
+    if constexpr (ODD) {
+      if (KT >= 3) {
+        ktile(even, ra, rb, a_off, b_off, a_slab, b_slab);
+        last_ktile();
+        ktile(odd, ra, rb, a_off, b_off, 0, 0);
+      } else {
+        last_ktile();
+      }
+      ktile(even, ra, rb, a_off, b_off, 0, 0);
+    } else {
+      last_ktile();
+      ktile(even, ra, rb, a_off, b_off, 0, 0);
+      ktile(odd, ra, rb, a_off, b_off, 0, 0);
+    }
+    GS_ACC_DONE(acc[7]);                       // the last eight MFMAs wrote row 7; the pipe is in order, so all are through
+
+    // ---- epilogue: C/D layout col = lane & 15, row = 4 (lane >> 4) + r.  A block alone writes 64-byte half-lines, so
+    // blocks j and j + 1 of a row go out back to back: a row's 32 consecutive floats leave together.
+    const int row0 = m0 + wm * 128 + 4 * lq, col0 = n0 + wn * 128 + l15;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+      for (int jp = 0; jp < 8; jp += 2) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = row0 + i * 16 + r;
+#pragma unroll
+          for (int j = jp; j < jp + 2; ++j) {
+            const int col = col0 + j * 16;
+            if (row < M && col < N) {
+              float* p = C + (int64_t)row * ldc + col;
+              float v;                       // (read where it is stored: hipcc otherwise copies all 256 at once and spills)
+              asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(acc[i][j][r]));
+              if (accumulate) v += *p;
+              *p = v;
+            }
+          }
+        }
+      }
+    }
+  };
+  if (KT & 1) tile(GsInt<1>{});
+  else tile(GsInt<0>{});
 #undef GS_MFMA
 #undef GS_ACC_ZEROED
 #undef GS_ACC_DONE
 #undef GS_READ_A
 #undef GS_READ_B
+#undef GS_FILL_A
+#undef GS_FILL_B
+#undef GS_FILL_NONE
 #undef GS_READS_DONE
 #undef GS_TIE8
-#undef GS_PIECE
-
-  // ---- epilogue: C/D layout col = lane & 15, row = 4 (lane >> 4) + r.  A block alone writes 64-byte half-lines, so
-  // blocks j and j + 1 of a row go out back to back: a row's 32 consecutive floats leave together.
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-#pragma unroll
-    for (int jp = 0; jp < 8; jp += 2) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm * 128 + i * 16 + 4 * lq + r;
-#pragma unroll
-        for (int j = jp; j < jp + 2; ++j) {
-          const int col = n0 + wn * 128 + j * 16 + l15;
-          if (row < M && col < N) {
-            float* p = C + (int64_t)row * ldc + col;
-            float v;                       // (read where it is stored: hipcc otherwise copies all 256 at once and spills)
-            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(acc[i][j][r]));
-            if (accumulate) v += *p;
-            *p = v;
-          }
-        }
-      }
-    }
-  }
+#undef GS_PIECE_LDS
+#undef GS_PIECE_M0
+#undef GS_PIECE_LOAD
 }
 
 // The fp32 kernel behind the flag: sp_gemm_glds_kernel's body, run only when an operand left the window.
