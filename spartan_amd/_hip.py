@@ -347,6 +347,9 @@ _EXTRAS_ABI = {
         'sp_sgd_mf': (C.c_int, [_i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp,
                                 C.POINTER(C.c_int64), _vp]),
     },
+    'spartan_hip_lmm.h': {
+        'sp_lmm_swaption': (C.c_int, [_i32, _vp, _i64, _i64, _i32, _i32, _f64, _f64, _f64, _f64, _vp, _vp]),
+    },
 }
 EXPORTS_EXTRAS = list(_EXTRAS_ABI['spartan_hip_extras.h'])
 EXPORTS_EIG = list(_EXTRAS_ABI['spartan_hip_eig.h'])
@@ -361,6 +364,7 @@ EXPORTS_NBODY = list(_EXTRAS_ABI['spartan_hip_nbody.h'])
 EXPORTS_CF = list(_EXTRAS_ABI['spartan_hip_cf.h'])
 EXPORTS_SVM = list(_EXTRAS_ABI['spartan_hip_svm.h'])
 EXPORTS_MF = list(_EXTRAS_ABI['spartan_hip_mf.h'])
+EXPORTS_LMM = list(_EXTRAS_ABI['spartan_hip_lmm.h'])
 KNN_MAX_K = 128       # SP_KNN_MAX_K of spartan_hip_knn.h
 CF_MAX_K = 128        # SP_CF_MAX_K of spartan_hip_cf.h (tests/test_cf_cases_cpu.py keeps the two equal)
 SP_ALS_MAX_F = 64     # of spartan_hip_als.h
@@ -368,6 +372,7 @@ SP_LDA_MAX_K = 128    # of spartan_hip_lda.h
 SP_NB_MAX_LABELS = 128   # of spartan_hip_nb.h
 SP_SVM_MAX_D = 4096      # of spartan_hip_svm.h
 SP_MF_MAX_F = 512        # of spartan_hip_mf.h
+SP_LMM_MAX_K = 128       # of spartan_hip_lmm.h (tests/test_swaption_cases_cpu.py keeps the two equal)
 SP_MF_WIDE = 64          # of spartan_hip_mf.h (tests/test_netflix_cases_cpu.py keeps header, binding and plans equal)
 SP_AFF_METRICS = {'rbf': 0, 'euclidean': 1, 'manhattan': 2}   # SP_AFF_* of spartan_hip_spectral.h
 
@@ -378,7 +383,7 @@ _extras = None
 def extras():
   """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn / knn_merge, apsp / graph_from_knn,
   als_solve, fuzzy_step, lda_step, affinity_degree / affinity_matrix, nb_step, nbody_accel, item_topk / item_topk_merge,
-  svm_dca, sgd_mf / sgd_mf_plan / sgd_mf_host);
+  svm_dca, sgd_mf / sgd_mf_plan / sgd_mf_host, lmm_swaption);
   raises if it has not been built.  What their Python side refuses: tile_checks.py."""
   global _extras
   if _extras is None:

@@ -22,6 +22,7 @@ from . import devarray as D
 from . import sparse as sparse_mod
 from .array import distarray, tile
 from .backend_hip_extras import ExtrasTileBodies
+from .backend_hip_lmm import LmmTileBodies
 from .backend_hip_mf import MfTileBodies
 from .backend_hip_svm import SvmTileBodies
 from .expr.local import LocalMapLocationExpr, FnCallExpr, LocalInput
@@ -393,7 +394,7 @@ def _no_copy(t):
   raise lower.NotLowerable('an operand the kernels cannot address in place')
 
 
-class HipBackend(ExtrasTileBodies, SvmTileBodies, MfTileBodies):
+class HipBackend(ExtrasTileBodies, SvmTileBodies, MfTileBodies, LmmTileBodies):
   name = 'hip'
 
   def __init__(self, device=None):

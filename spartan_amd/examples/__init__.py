@@ -23,5 +23,8 @@ loop over its rows, w on chip) per row band and iteration and forms w with the r
 reduce kernels;
 `netflix.sgd` (stochastic-gradient matrix factorisation of a sparse rating matrix) runs one sp_sgd_mf (a block's
 sequential loop over its ratings, level-scheduled, with the loop's bits) per block of a stratum and updates the factors
-in place through select / update_slice.
+in place through select / update_slice;
+`swaption.simulate` (European payer swaptions under the LIBOR market model by Monte Carlo) runs one sp_lmm_swaption (all
+time steps of a band's antithetic pairs of paths, the forward rates on chip) per column band of a product's draws and
+forms mean and standard error with the reference's expressions on the map and reduce kernels.
 Like `sort` they are imported on first use, not with the package."""

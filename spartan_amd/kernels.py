@@ -770,6 +770,26 @@ def svm_dca(x, y, alpha, w0, scaled_lambda, chains, alpha_out, w_out=None):
   return alpha_out, w_out
 
 
+@_writes('out')
+def lmm_swaption(eps, maturities, lamb, delta, f0, theta, out):
+  """out[p] <- the discounted payoff of one swaption under the LIBOR market model, the mean over the antithetic pair p
+  of paths (sp_lmm_swaption; include/spartan_hip_lmm.h states the recurrence, operation for operation): `eps` [S, n]
+  fp32 or fp64 draws, a view with inner stride 1 (a band of columns of a wider array is taken as it is); `out` [n] of
+  its dtype, contiguous.  TypeError for other or mixed dtypes, ValueError for S and K = `maturities` that do not satisfy
+  1 <= S < K <= SP_LMM_MAX_K, scalars that are not finite, delta <= 0 or a target that does not fit -- all before any
+  launch.  One kernel (none for n = 0), no workspace.  Nothing waits for the device."""
+  _require_device(eps, out)
+  dt, n, s, k, lamb, delta, f0, theta = tile_checks.check_lmm_swaption(np_dtype_of(eps), eps.shape, maturities, lamb,
+                                                                       delta, f0, theta)
+  tile_checks.one_float_dtype('lmm_swaption', _dtypes(eps, out))
+  if tuple(out.shape) != (n,):
+    raise ValueError('lmm_swaption: a target of shape %s for %d pairs' % (tuple(out.shape), n))
+  assert out.is_contiguous()
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  check(lib.sp_lmm_swaption(_hip.sp_dtype(dt), _p(eps), _ld(eps), n, s, k, lamb, delta, f0, theta, _p(out), _stream()))
+  return out
+
+
 def sgd_mf_plan(m, n, indptr, indices):
   """The level schedule of a tile of ratings [m, n] in canonical CSR (sp_sgd_mf_plan; include/spartan_hip_mf.h states
   its layout) from HOST arrays `indptr` [m + 1] and `indices` [nnz]: a uint8 array of the bytes in use.  Host code: no

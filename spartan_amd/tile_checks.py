@@ -411,3 +411,34 @@ def check_sgd_mf(dtypes, tile_shape, u_shape, m_shape, lr=None, what='sgd_mf'):
   if not np.isfinite(lt):
     raise ValueError('%s: lr = %r must be finite in %s' % (what, lr, dtypes[0]))
   return dtypes[0], m, n, f, lr
+
+
+def check_lmm_swaption(dtype, shape, maturities, lamb, delta, f0, theta, steps=None, what='lmm_swaption'):
+  """(dtype, n, S, K, lamb, delta, f0, theta) of one swaption's paths from draws eps [S, n] -- `dtype` and `shape` are
+  theirs -- over K = `maturities` forward rates, or what sp_lmm_swaption refuses: TypeError ("astype first") for draws
+  that are not float32 / float64; ValueError for draws that are not 2-D (with `steps` rows, where the caller names
+  them), S and K that do not satisfy 1 <= S < K <= SP_LMM_MAX_K, a lamb, delta, f0 or theta that is not finite in the
+  draws' dtype, and delta <= 0.  The one copy: the launcher, the backend, the NumPy body of examples/_swaption.py and
+  the driver all refuse through it."""
+  dtype = np.dtype(dtype)
+  if dtype not in _hip.FLOATS:
+    raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, dtype))
+  shape = tuple(int(v) for v in shape)
+  if len(shape) != 2 or (steps is not None and shape[0] != int(steps)):
+    raise ValueError('%s: expected draws of shape (%s, n), got %s' % (what, 'steps' if steps is None else int(steps), shape))
+  s, n = shape
+  k = int(maturities)
+  if not 1 <= s < k <= _hip.SP_LMM_MAX_K:
+    raise ValueError('%s: steps = %d and maturities = %d must satisfy 1 <= steps < maturities <= %d'
+                     % (what, s, k, _hip.SP_LMM_MAX_K))
+  scalars = []
+  for name, value in (('lamb', lamb), ('delta', delta), ('f0', f0), ('theta', theta)):
+    value = float(value)
+    with np.errstate(all='ignore'):
+      vt = dtype.type(value)
+    if not np.isfinite(vt):
+      raise ValueError('%s: %s = %r must be finite in %s' % (what, name, value, dtype))
+    if name == 'delta' and not vt > 0:
+      raise ValueError('%s: delta = %r must be > 0 in %s' % (what, value, dtype))
+    scalars.append(value)
+  return (dtype, n, s, k) + tuple(scalars)
