@@ -342,6 +342,11 @@ size_t sp_gemm_workspace_bytes(int32_t dtype, int64_t M, int64_t N, int64_t K);
  * sp_gemm_split_workspace_bytes(...) bytes (0: the shape stays on the kernels above; a caller hands sp_gemm_ws the
  * larger of the two sizes).  SP_GEMM_SPLIT=0 in the environment, read once, makes it 0 everywhere. */
 size_t sp_gemm_split_workspace_bytes(int32_t dtype, int64_t M, int64_t N, int64_t K);
+/* The order in which the split tier's mainloop hands out its 256 x 256 tiles, computed on the host by the function
+ * the kernel compiles: block b of a launch over tiles_m x tiles_n tiles takes tile (tm[b], tn[b]), b < tiles_m *
+ * tiles_n.  Returns the number of blocks filled in; 0 for a grid with no tiles, with a side of more than 2^23
+ * tiles (M, N < 2^31 give no more) or with 2^31 - 1 tiles and more. */
+int32_t sp_gemm_split_walk(int32_t tiles_m, int32_t tiles_n, int32_t* tm, int32_t* tn);
 int sp_gemm_ws(int32_t dtype, const void* d_A, int64_t lda, const void* d_B, int64_t ldb, void* d_C,
                int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t accumulate, void* d_ws,
                size_t ws_bytes, void* stream);

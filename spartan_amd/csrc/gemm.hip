@@ -933,6 +933,23 @@ extern "C" size_t sp_gemm_split_workspace_bytes(int32_t dtype, int64_t M, int64_
   return sp_gemm_bf16_ws_bytes(M, N, K);
 }
 
+// The split tier's walk on the host: block b of a tiles_m x tiles_n launch takes tile (tm[b], tn[b]), by the very
+// function the mainloop compiles.  Returns the number of blocks, 0 for a grid no launch can have (a side of more than
+// 2^23 tiles, 2^31 - 1 tiles or more).
+extern "C" int32_t sp_gemm_split_walk(int32_t tiles_m, int32_t tiles_n, int32_t* tm, int32_t* tn) {
+  if (tiles_m < 1 || tiles_n < 1 || tiles_m > (1 << 23) || tiles_n > (1 << 23) || !tm || !tn ||
+      (int64_t)tiles_m * tiles_n >= 2147483647LL)
+    return 0;
+  const int nblk = tiles_m * tiles_n;
+  for (int b = 0; b < nblk; ++b) {
+    int m, n;
+    sp_gemm_split_tile_of_block(b, nblk, tiles_m, tiles_n, m, n);
+    tm[b] = m;
+    tn[b] = n;
+  }
+  return nblk;
+}
+
 extern "C" size_t sp_gemm_workspace_bytes(int32_t dtype, int64_t M, int64_t N, int64_t K) {
   if (M < 1 || N < 1 || (dtype != SP_F32 && dtype != SP_F64)) return 0;
   const SplitPlan pl = sp_split_plan(M, N, K, dtype == SP_F32 ? 16 : 8);

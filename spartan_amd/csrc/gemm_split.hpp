@@ -57,7 +57,19 @@
 //
 // MAINLOOP (sp_gemm_glds_kernel_bf16x3).  256 x 256 workgroup tile, one workgroup per CU, 2 x 2 waves of 128 x 128
 // each, one per SIMD with all 512 registers: the 8 x 8 accumulator blocks of 16 x 16 fill the 256 AGPRs, the
-// fragments live in VGPRs.  k-tiles of 16 are brought by global_load_lds_dwordx4 into two LDS stages.  The MFMA is
+// fragments live in VGPRs.  Tiles are handed out by a walk of the kernel's own (sp_gemm_split_tile_of_block; the fp32
+// kernels keep sp_gemm_tile_of_block and GROUP_M, fitted to 256 x 128 tiles, two workgroups per CU and row-major A).
+// A workgroup loads one A panel and one B panel per k-tile, 24 KiB each, and the 32 workgroups resident on an XCD run
+// in step, so what that XCD's L2 fetches from beyond it per k-tile is the DISTINCT tile rows plus tile columns among
+// its 32 tiles: measured (2 x FETCH_SIZE, 8192^3) 13.29 / 7.25 / 4.83 / 4.83 / 7.25 GB per launch for windows of
+// 1 x 32 / 2 x 16 / 4 x 8 / 8 x 4 / 16 x 2 tiles, which is 33 / 18 / 12 / 12 / 18 panels x 24 KiB x 512 k-tiles x 32
+// windows to the last digit -- the model with no drift in k at all.  So the window is 4 x 8 (no 32 tiles touch fewer
+// than 12 panels), m-fastest inside.  Across XCDs the eight windows of a round of 256 workgroups tile one 16 x 16
+// rectangle of tiles, so that a round asks the fabric for 16 + 16 distinct panels, each from two or four XCDs, and not,
+// as with a contiguous range of the tile order per XCD, for 32 + 8 with all eight XCDs on the same 8 B panels at
+// once: same L2 traffic, 0.7 % less time on the headline, and the only arrangement that clears the project's bar
+// (profiles/gemm_split_tile_walk_notes.md).  No workgroup waits for another: the walk is a function of the block id.
+// k-tiles of 16 are brought by global_load_lds_dwordx4 into two LDS stages.  The MFMA is
 // v_mfma_f32_16x16x32_bf16 (under this loop the chip holds a higher clock on it than on 32x32x16: measured in
 // profiles/gemm_split_mfma_shape_notes.md), whose 32 k carry TWO terms of the same 16 k: lanes 0-31 of an operand
 // (k-groups 0, 1) hold the 16 k of one image, lanes 32-63 (k-groups 2, 3) the same 16 k of another.  Three MFMAs per
@@ -124,6 +136,44 @@ struct GsCfg {
   static_assert(NPIECES * 8 <= NMFMA / 2, "one piece after every eighth MFMA of the first half");
   static_assert(STAGE_BYTES + 7 * 16 * GS_RB < 65536, "stage and block go into a ds_read's 16-bit offset");
 };
+
+// ---- the walk: block id -> tile of the mainloop (see MAINLOOP above) --------------------------------------------------
+constexpr int GS_WALK_RH = 4;                     // tile rows of an XCD's window of 32 resident tiles; its columns: 32 / RH
+constexpr int GS_WALK_SUPER = 16;                 // tile rows and columns of the rectangle the eight windows of a round tile
+constexpr int GS_WALK_ROUND = 8 * 32;             // workgroups resident at once: 8 XCDs x 32 CUs
+static_assert(32 % GS_WALK_RH == 0 && GS_WALK_SUPER % GS_WALK_RH == 0 &&
+              GS_WALK_SUPER * GS_WALK_SUPER == GS_WALK_ROUND, "eight RH x 32 / RH windows tile the super-rectangle");
+
+// A bijection from block ids onto tiles for every grid and block count nblk = tiles_m * tiles_n (tiles_m, tiles_n <=
+// 2^23, what M, N < 2^31 give; tests/test_gemm_split_walk.py).  Position p of a block in THE ORDER: blocks bid, bid + 8,
+// .. run on one XCD, so in a full round of 256 XCD x takes positions 32 x .. 32 x + 31 of the round; the blocks behind
+// the last full round share out what is left in contiguous ranges, as sp_gemm_tile_of_block does.  THE ORDER itself:
+// bands of SUPER tile rows; in a band, rectangles of SUPER tile columns; in a rectangle, strips of RH tile rows; in a
+// strip, m-fastest -- each level clipped at the grid's edge, so every level holds whole numbers of the next one.
+__host__ __device__ __forceinline__ void sp_gemm_split_tile_of_block(int bid, int nblk, int tiles_m, int tiles_n,
+                                                                     int& tm, int& tn) {
+  constexpr int S = GS_WALK_SUPER, RH = GS_WALK_RH;
+  const int xcd = bid & 7, local = bid >> 3;
+  const int full = nblk & ~(GS_WALK_ROUND - 1);
+  int p;
+  if (bid < full) {
+    p = (local >> 5) * GS_WALK_ROUND + xcd * 32 + (local & 31);
+  } else {
+    const int rest = nblk - full, q = rest >> 3, r = rest & 7;
+    p = full + (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + ((bid - full) >> 3);
+  }
+  const int band = p / (S * tiles_n);
+  const int h1 = (tiles_m - band * S) < S ? (tiles_m - band * S) : S;           // the band's tile rows
+  int q = p - band * S * tiles_n;
+  const int rect = q / (h1 * S);
+  const int w2 = (tiles_n - rect * S) < S ? (tiles_n - rect * S) : S;           // the rectangle's tile columns
+  q -= rect * h1 * S;
+  const int strip = q / (RH * w2);
+  const int h3 = (h1 - strip * RH) < RH ? (h1 - strip * RH) : RH;               // the strip's tile rows
+  q -= strip * RH * w2;
+  tm = band * S + strip * RH + q % h3;
+  tn = rect * S + q / h3;
+}
 
 template <int V>
 struct GsInt {                                    // a constant handed to a generic lambda
@@ -402,7 +452,7 @@ __global__ __launch_bounds__(GsCfg::THREADS, 1) void sp_gemm_glds_kernel_bf16x3(
   auto tile = [&](auto odd_count_) __attribute__((always_inline)) {
     constexpr bool ODD = decltype(odd_count_)::value != 0;
     int tm, tn;
-    sp_gemm_tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n, tm, tn);
+    sp_gemm_split_tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n, tm, tn);
     const int m0 = tm * G::BM, n0 = tn * G::BN;
     unsigned a_off[PW], b_off[PW];
     piece_offsets(m0, M, a_off);
