@@ -352,6 +352,12 @@ _EXTRAS_ABI = {
     'spartan_hip_lmm.h': {
         'sp_lmm_swaption': (C.c_int, [_i32, _vp, _i64, _i64, _i32, _i32, _f64, _f64, _f64, _f64, _vp, _vp]),
     },
+    'spartan_hip_canopy.h': {
+        'sp_canopy': (C.c_int, [_i32, _vp, _i64, _i64, _i64, _f64, _f64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _sz,
+                                _vp]),
+        'sp_canopy_workspace_bytes': (_sz, [_i32, _i64, _i64, _i64, _i64]),
+        'sp_pdf_label': (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
+    },
 }
 EXPORTS_EXTRAS = list(_EXTRAS_ABI['spartan_hip_extras.h'])
 EXPORTS_EIG = list(_EXTRAS_ABI['spartan_hip_eig.h'])
@@ -367,6 +373,7 @@ EXPORTS_CF = list(_EXTRAS_ABI['spartan_hip_cf.h'])
 EXPORTS_SVM = list(_EXTRAS_ABI['spartan_hip_svm.h'])
 EXPORTS_MF = list(_EXTRAS_ABI['spartan_hip_mf.h'])
 EXPORTS_LMM = list(_EXTRAS_ABI['spartan_hip_lmm.h'])
+EXPORTS_CANOPY = list(_EXTRAS_ABI['spartan_hip_canopy.h'])
 KNN_MAX_K = 128       # SP_KNN_MAX_K of spartan_hip_knn.h
 CF_MAX_K = 128        # SP_CF_MAX_K of spartan_hip_cf.h (tests/test_cf_cases_cpu.py keeps the two equal)
 SP_ALS_MAX_F = 64     # of spartan_hip_als.h
@@ -385,7 +392,7 @@ _extras = None
 def extras():
   """The library of kernels outside the tile path (sort, potrf / trsm_rlt / syevj, knn / knn_merge, apsp / graph_from_knn,
   als_solve, fuzzy_step, lda_step, affinity_degree / affinity_matrix, nb_step, nbody_accel, item_topk / item_topk_merge,
-  svm_dca, sgd_mf / sgd_mf_plan / sgd_mf_host, lmm_swaption);
+  svm_dca, sgd_mf / sgd_mf_plan / sgd_mf_host, lmm_swaption, canopy / pdf_label);
   raises if it has not been built.  What their Python side refuses: tile_checks.py."""
   global _extras
   if _extras is None:

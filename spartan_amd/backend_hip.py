@@ -21,6 +21,7 @@ from . import _hip, kernels, lower
 from . import devarray as D
 from . import sparse as sparse_mod
 from .array import distarray, tile
+from .backend_hip_canopy import CanopyTileBodies
 from .backend_hip_extras import ExtrasTileBodies
 from .backend_hip_lmm import LmmTileBodies
 from .backend_hip_mf import MfTileBodies
@@ -394,7 +395,7 @@ def _no_copy(t):
   raise lower.NotLowerable('an operand the kernels cannot address in place')
 
 
-class HipBackend(ExtrasTileBodies, SvmTileBodies, MfTileBodies, LmmTileBodies):
+class HipBackend(ExtrasTileBodies, SvmTileBodies, MfTileBodies, LmmTileBodies, CanopyTileBodies):
   name = 'hip'
 
   def __init__(self, device=None):

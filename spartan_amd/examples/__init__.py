@@ -26,5 +26,8 @@ sequential loop over its ratings, level-scheduled, with the loop's bits) per blo
 in place through select / update_slice;
 `swaption.simulate` (European payer swaptions under the LIBOR market model by Monte Carlo) runs one sp_lmm_swaption (all
 time steps of a band's antithetic pairs of paths, the forward rates on chip) per column band of a product's draws and
-forms mean and standard error with the reference's expressions on the map and reduce kernels.
+forms mean and standard error with the reference's expressions on the map and reduce kernels;
+`canopy_clustering.canopy_cluster` / `find_centers` (canopy clustering) runs one sp_canopy (a tile's whole greedy loop
+over its rows and its growing list of canopies, with the loop's bytes) per row tile and once more over the tiles'
+centres, and labels every row tile with one sp_pdf_label in a lazy shuffle.
 Like `sort` they are imported on first use, not with the package."""

@@ -790,6 +790,55 @@ def lmm_swaption(eps, maturities, lamb, delta, f0, theta, out):
   return out
 
 
+@_writes('centers', 'counts', 'rows', 'num')
+def canopy(x, t1, t2, chains, cap, centers, counts, rows, num):
+  """The greedy canopy pass of the reference over the rows of a tile (sp_canopy; include/spartan_hip_canopy.h states
+  the arithmetic and the order of a canopy's sum): `x` [n, d] fp32 or fp64, a view with inner stride 1, cut into
+  `chains` consecutive bands.  Chain c writes its canopies in creation order to the slots c * cap .. of `centers`
+  [chains * cap, d] of x's dtype (the means; a view with inner stride 1), `counts` and `rows` [chains * cap] int64
+  contiguous (the observed rows; the creating row's index in x), and their number -- or -1 where `cap` does not suffice
+  -- to `num` [chains] int64.  TypeError for other or mixed dtypes, ValueError for d < 1, chains < 1, cap < 1,
+  thresholds that are not finite or targets that do not fit -- all before any launch.  One kernel; owns the workspace.
+  Nothing waits for the device."""
+  _require_device(x, centers, counts, rows, num)
+  dt, n, d, t1, t2, chains, cap, _ = tile_checks.check_canopy(np_dtype_of(x), x.shape, t1, t2, chains, cap)
+  tile_checks.one_float_dtype('canopy', _dtypes(x, centers))
+  slots = chains * cap
+  if tuple(centers.shape) != (slots, d) or any(tuple(t.shape) != s for t, s in ((counts, (slots,)), (rows, (slots,)),
+                                                                               (num, (chains,)))):
+    raise ValueError('canopy: targets of shapes %s for %d chains of at most %d canopies and %d features'
+                     % ([tuple(t.shape) for t in (centers, counts, rows, num)], chains, cap, d))
+  if any(np_dtype_of(t) != np.int64 for t in (counts, rows, num)):
+    raise TypeError('canopy: counts, rows and num are int64, got %s' % ([np_dtype_of(t) for t in (counts, rows, num)],))
+  assert all(t.is_contiguous() for t in (counts, rows, num))
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  code = _hip.sp_dtype(dt)
+  ws = _ws.get(lib.sp_canopy_workspace_bytes(code, n, d, chains, cap), x.device)
+  check(lib.sp_canopy(code, _p(x), _ld(x), n, d, t1, t2, chains, cap, _p(centers), _ld(centers), _p(counts), _p(rows),
+                      _p(num), _p(ws), ws.numel(), _stream()))
+  return centers, counts, rows, num
+
+
+@_writes('labels')
+def pdf_label(x, centers, labels):
+  """labels[i] <- the lowest j at which 1 / (1 + |x_i - c_j|^2) is largest, -1 where there is none (sp_pdf_label;
+  include/spartan_hip_canopy.h says why this is not an arg-min of the distance): `x` [n, d] and `centers` [k, d] fp32
+  or fp64 alike, views with inner stride 1; `labels` [n] int32 contiguous.  TypeError for other or mixed dtypes and a
+  target that is not int32, ValueError for shapes that do not fit -- all before any launch.  One kernel (none for
+  n = 0), no workspace.  Nothing waits for the device."""
+  _require_device(x, centers, labels)
+  dt, n, k, d = tile_checks.check_pdf_label(_dtypes(x, centers), (x.shape, centers.shape))
+  if tuple(labels.shape) != (n,):
+    raise ValueError('pdf_label: a target of shape %s for %d rows' % (tuple(labels.shape), n))
+  if np_dtype_of(labels) != np.int32:
+    raise TypeError('pdf_label: labels are int32, got %s' % (np_dtype_of(labels),))
+  assert labels.is_contiguous()
+  lib = _hip.extras()        # (outside the tile path: libspartan_hip_extras.so)
+  check(lib.sp_pdf_label(_hip.sp_dtype(dt), _p(x), _ld(x), n, _p(centers) if k else None, _ld(centers), k, d, _p(labels),
+                         _stream()))
+  return labels
+
+
 def sgd_mf_plan(m, n, indptr, indices):
   """The level schedule of a tile of ratings [m, n] in canonical CSR (sp_sgd_mf_plan; include/spartan_hip_mf.h states
   its layout) from HOST arrays `indptr` [m + 1] and `indices` [nnz]: a uint8 array of the bytes in use.  Host code: no

@@ -442,3 +442,74 @@ def check_lmm_swaption(dtype, shape, maturities, lamb, delta, f0, theta, steps=N
       raise ValueError('%s: delta = %r must be > 0 in %s' % (what, value, dtype))
     scalars.append(value)
   return (dtype, n, s, k) + tuple(scalars)
+
+
+def _canopy_floats(what, dtypes):
+  dtypes = [np.dtype(d) for d in dtypes]
+  for d in dtypes:
+    if d not in _hip.FLOATS:
+      raise TypeError('%s: dtype %s is not supported (float32 float64); convert with astype first' % (what, d))
+  for d in dtypes[1:]:
+    if d != dtypes[0]:
+      raise TypeError('%s: operands of two dtypes (%s, %s); convert with astype first' % (what, dtypes[0], d))
+  return dtypes[0]
+
+
+_NO_CF = object()
+
+
+def check_canopy(dtype, shape, t1, t2, chains=1, cap=None, cf=_NO_CF, what='canopy'):
+  """(dtype, n, d, t1, t2, chains, cap, cf) of the greedy canopy pass over points x [n, d] -- `dtype` and `shape` are
+  theirs -- or what sp_canopy refuses: TypeError ("astype first") for points that are not float32 / float64; ValueError
+  for points that are not 2-D, d < 1, chains < 1, cap < 1, and a t1 or t2 that is not finite in the points' dtype.
+  cap = None is min(the longest chain's rows, 1024), at least 1.  `cf`, the caller's filter `count > cf`, is returned as
+  an int (None where the caller gives none): ValueError for one that is not an integer.  The one copy: the launcher, the backend, the
+  NumPy body of examples/_canopy.py and the driver all refuse through it."""
+  dtype = _canopy_floats(what, [dtype])
+  shape = tuple(int(v) for v in shape)
+  if len(shape) != 2:
+    raise ValueError('%s: expected points of shape (n, d), got %s' % (what, shape))
+  n, d = shape
+  if d < 1:
+    raise ValueError('%s: d = %d must be at least 1' % (what, d))
+  chains = int(chains)
+  if chains < 1:
+    raise ValueError('%s: chains = %d must be at least 1' % (what, chains))
+  if cap is None:
+    cap = max(min(-(-n // chains), 1024), 1)
+  cap = int(cap)
+  if cap < 1:
+    raise ValueError('%s: cap = %d must be at least 1' % (what, cap))
+  scalars = []
+  for name, value in (('t1', t1), ('t2', t2)):
+    value = float(value)
+    with np.errstate(all='ignore'):
+      vt = dtype.type(value)
+    if not np.isfinite(vt):
+      raise ValueError('%s: %s = %r must be finite in %s' % (what, name, value, dtype))
+    scalars.append(value)
+  if cf is _NO_CF:
+    cf = None
+  else:
+    if isinstance(cf, (bool, np.bool_)) or not isinstance(cf, (int, np.integer)):
+      raise ValueError('%s: cf = %r must be an integer' % (what, cf))
+    cf = int(cf)
+  return dtype, n, d, scalars[0], scalars[1], chains, cap, cf
+
+
+def check_pdf_label(dtypes, shapes, what='pdf_label'):
+  """(dtype, n, k, d) of the labels of points x [n, d] among centres [k, d] -- `dtypes` and `shapes` are theirs, in
+  that order -- or what sp_pdf_label refuses: TypeError ("astype first") for arrays that are not float32 / float64 or
+  that are of two dtypes; ValueError for points or centres that are not 2-D, feature counts that differ and d < 1.
+  k = 0 is accepted (every label is -1).  The one copy, as check_canopy."""
+  dtype = _canopy_floats(what, dtypes)
+  x, c = (tuple(int(v) for v in s) for s in shapes)
+  if len(x) != 2:
+    raise ValueError('%s: expected points of shape (n, d), got %s' % (what, x))
+  if len(c) != 2:
+    raise ValueError('%s: expected centers of shape (k, d), got %s' % (what, c))
+  if x[1] != c[1]:
+    raise ValueError('%s: points of %d features and centers of %d' % (what, x[1], c[1]))
+  if x[1] < 1:
+    raise ValueError('%s: d = %d must be at least 1' % (what, x[1]))
+  return dtype, x[0], c[0], x[1]
