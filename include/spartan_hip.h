@@ -529,6 +529,8 @@ int sp_coo_reshape(int64_t nnz, int32_t* d_rows, int32_t* d_cols, int64_t old_co
  * span chunks added by a fix-up pass in chunk order -- no floating-point atomics; needs the workspace);
  * n == 1, rows of >= 1024 entries on average (or no workspace): 2..64 lanes per row, shuffle reduction; n > 1: entries of a row in storage order
  * (scipy's csr_matvecs order).  Without a workspace the lanes-per-row kernel is used for every n == 1.
+ * accumulate: every n == 1 kernel sums the row from 0 and adds the sum to C last (C + s; the carries of a row that
+ * spans chunks after that, in chunk order); n > 1 starts from C and adds the row's terms to it one by one.
  * d_plan (may be NULL): the output of sp_csr_spmv_plan for this matrix -- the first row that starts in each
  * 2048-entry chunk, the length of the longest row and an arrival counter, sp_csr_spmv_plan_entries(nnz) int64 values
  * -- computed once per matrix and reused by every multiply (an iteration like p <- W.p keeps W).  With a plan the
